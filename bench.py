@@ -8,8 +8,13 @@ examples/ipopt_callbacks_exp.jl:11-31 without the spline map.  Inputs (u) are re
 in HBM before the timed region.  Seeds are sharded across ranks (weak scaling); the only
 collective is the RCCL all-gather of each rank's best (J, seed) per step.
 
-Run:  python bench.py [--gpus N --steps K --warmup W --config cavity --call-form fused]
+Run:  python bench.py [--gpus N --steps K --warmup W --config cavity --call-form fused] [--full] [--dump-outputs DIR]
       python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N
+
+A plain run sets up, warms up, times the K steps and prints the result line (with the roofline figures of the timed steps'
+own phase events).  --full adds what runs beside the metric: the CPU baseline and the parity check against it, and the
+side legs (the other configs and the split call form).  --dump-outputs DIR writes what the last timed step returned
+(J, dJdu or dJdc, best) as DIR/<name>.npy; the inputs are seeded, so two builds can be compared output for output.
 
 --call-form: "fused" (default) one device call per eval (qoc_eval_dev); "split" the reference's own call form,
 qoc_propagate_dev then qoc_grape_sensitivity_dev (Ipopt's f then f_grad, examples/ipopt_callbacks_exp.jl:11-31) on the
@@ -342,6 +347,25 @@ def side_legs(spec, local_rank, order, steps, warmup, parity_seeds=4):
     return out
 
 
+DUMP_MAX_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, rank=0):
+    """Write each array as <path>/<name>.npy (rank r > 0: <name>.rank<r>.npy), float32 arrays as they are and the
+    rest as float64.  All of them together stay under DUMP_MAX_BYTES: an array above its even share of that is cut
+    to a fixed sample of its flattened entries (seeded by the array's size, so the same entries in every run)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_MAX_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        a = np.ascontiguousarray(a, dtype=np.float32 if a.dtype == np.float32 else np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(a.size).choice(a.size, share // a.itemsize, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + (f".rank{rank}" if rank else "") + ".npy"), a)
+
+
 def launch_ranks(n: int) -> int:
     """Start n ranks of this script (torch.distributed.run, rendezvous on 127.0.0.1) and return their exit
     code.  Called before anything touches the GPU: the ranks are child processes, this one only waits."""
@@ -403,16 +427,23 @@ def main():
     ap.add_argument("--config", default="cavity", choices=sorted(WORKLOADS))
     ap.add_argument("--order", type=int, default=3)
     ap.add_argument("--seeds", type=int, default=0, help="override seeds per GPU")
-    ap.add_argument("--no-cpu", action="store_true")
-    ap.add_argument("--cpu-seconds", type=float, default=12.0)
+    ap.add_argument("--no-cpu", action="store_true", help="with --full: leave the CPU baseline and its parity check out")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="with --full: CPU time of the baseline's sample")
     ap.add_argument("--call-form", default="fused", choices=["fused", "split", "ipopt"],
                     help="fused: qoc_eval_dev; split: qoc_propagate_dev + qoc_grape_sensitivity_dev; ipopt: the spline "
                          "callbacks qoc_propagate_spline + qoc_sensitivity_spline on host coefficients")
     ap.add_argument("--side", default=None,
-                    help="comma list of config:form legs timed after the main line (rank 0, N = 1; default: the "
-                         "other BASELINE configs when the main config is the default one, none otherwise; '' for none)")
+                    help="with --full: comma list of config:form legs timed after the main line (rank 0, N = 1; default: "
+                         "the other BASELINE configs when the main config is the default one, none otherwise; '' for "
+                         "none)")
     ap.add_argument("--cpu-plumbing", action="store_true",
                     help="no GPU: check the launcher and the best-(J, seed) exchange over gloo (CPU tests)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the legs beside the metric: the CPU baseline with the parity "
+                         "check against it (--no-cpu, --cpu-seconds) and the side legs (--side); off by default")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps write what the last timed step returned (J, dJdu or dJdc, best) as "
+                         "DIR/<name>.npy (ranks above 0: DIR/<name>.rank<r>.npy)")
     args = ap.parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -478,6 +509,8 @@ def main():
     if world == 1:  # nothing to exchange: the evals that reduce their own J write the best pair here themselves
         eng.set_best_output(best_d.data_ptr())
 
+    host_out = {}  # ipopt form: the host arrays the spline callbacks return
+
     def step():
         if args.call_form == "fused":
             eng.eval_device(u_d.data_ptr(), args.order, J_d.data_ptr(), g_d.data_ptr())
@@ -485,8 +518,8 @@ def main():
             eng.propagate_device(u_d.data_ptr(), J_d.data_ptr())
             eng.grape_sensitivity_device(u_d.data_ptr(), args.order, g_d.data_ptr())
         else:
-            eng.propagate_spline(coef)
-            eng.sensitivity_spline(coef, args.order)
+            host_out["J"] = eng.propagate_spline(coef)
+            host_out["dJdc"] = eng.sensitivity_spline(coef, args.order)
         if transport in ("rccl-libqoc", "local"):
             eng.allgather_best_device(best_d.data_ptr())  # on the engine stream, after its kernels
         elif world > 1:
@@ -548,8 +581,15 @@ def main():
         dist.all_reduce(el, op=dist.ReduceOp.MAX)
     elapsed = float(el.item())
 
+    if args.dump_outputs:
+        # what a caller of the timed path holds after the last step: the device arrays J (B,), dJdu (B, Nt, nu) of the
+        # device call forms, the spline callbacks' J (B,), dJdc (B, ns, nu) of the ipopt form, and the best (J, seed)
+        outs = dict(host_out) if args.call_form == "ipopt" else {"J": J_d.cpu().numpy(), "dJdu": g_d.cpu().numpy()}
+        outs["best"] = best_d.cpu().numpy()
+        dump_outputs(args.dump_outputs, outs, rank)
+
     phases = eng.phase_times()
-    if args.call_form == "ipopt":  # the parity leg checks the split kernels on the spline controls' u
+    if args.call_form == "ipopt" and args.full:  # the parity leg checks the split kernels on the spline controls' u
         eng.propagate_device(u_d.data_ptr(), J_d.data_ptr())
         eng.grape_sensitivity_device(u_d.data_ptr(), args.order, g_d.data_ptr())
         eng.synchronize()
@@ -941,7 +981,7 @@ def main():
     best = best_d.cpu().numpy().tolist()
     cpu = None
     parity = None
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         nthreads = cpu_threads()
         try:
             if large:
@@ -969,7 +1009,7 @@ def main():
     comm_ranks = eng.comm_ranks()
     spec = args.side if args.side is not None else (SIDE_LEGS if args.config == "cavity" and args.call_form == "fused"
                                                     and not args.seeds else "")
-    if rank == 0 and world == 1 and spec:
+    if rank == 0 and world == 1 and args.full and spec:
         eng.close()
         eng = None
         side = side_legs(spec, local_rank, args.order, max(args.steps, 5), max(args.warmup, 2))
