@@ -61,11 +61,15 @@ struct BlksegParams {
   // BLKSEG_BWD); stale: the stale-u flag of the check queued before BLKSEG_BWD (nonzero: the launch writes nothing)
   double2* gseg;
   const int* stale;
+  // the shifted generators' blocks, block-major [nblk][3][NB^2] (zeros for j > nu and for a padded row): built by the
+  // host where the block layout and the shifted generators are established, copied to LDS by the prologue
+  const double2* gtab;
 };
 enum { BLKSEG_FUSED = 0, BLKSEG_FWD = 1, BLKSEG_BWD = 2 };
 
 // LDS, in doubles: shifted generator blocks [nblk][3][E] complex | step records [Nt][4] | segment products [S][E][nblk]
-// complex | G_0 [E][nblk] complex | x_0 then x_N (N m complex) | λ_N coefficients (2 m complex) | scratch (24) |
+// complex | G_0 [E][nblk] complex | x_0 then x_N (N m complex) | X_target (N m complex) | λ_N coefficients (2 m
+// complex) | scratch (24) |
 // per-wave partial sums [W][RB][64][2] | dJdu [Nt][nu]
 __host__ __device__ inline size_t blkseg_off_rec(int NB, int nblk) { return (size_t)6 * NB * NB * nblk; }
 __host__ __device__ inline size_t blkseg_off_slot(int NB, int nblk, int Nt) { return blkseg_off_rec(NB, nblk) + 4 * (size_t)Nt; }
@@ -75,8 +79,11 @@ __host__ __device__ inline size_t blkseg_off_g0(int NB, int nblk, int Nt, int S)
 __host__ __device__ inline size_t blkseg_off_xN(int NB, int nblk, int Nt, int S) {
   return blkseg_off_g0(NB, nblk, Nt, S) + (size_t)2 * NB * NB * nblk;
 }
-__host__ __device__ inline size_t blkseg_off_cf(int N, int m, int NB, int nblk, int Nt, int S) {
+__host__ __device__ inline size_t blkseg_off_xt(int N, int m, int NB, int nblk, int Nt, int S) {
   return blkseg_off_xN(NB, nblk, Nt, S) + (size_t)2 * N * m;
+}
+__host__ __device__ inline size_t blkseg_off_cf(int N, int m, int NB, int nblk, int Nt, int S) {
+  return blkseg_off_xt(N, m, NB, nblk, Nt, S) + (size_t)2 * N * m;
 }
 __host__ __device__ inline size_t blkseg_off_red(int N, int m, int NB, int nblk, int Nt, int S) {
   return blkseg_off_cf(N, m, NB, nblk, Nt, S) + (size_t)4 * m;
@@ -90,6 +97,8 @@ __host__ __device__ inline size_t blkseg_off_dJ(int N, int m, int NB, int nblk, 
 __host__ __device__ inline size_t blkseg_lds(int N, int m, int nu, int NB, int nblk, int Nt, int S, int W, int RB) {
   return (blkseg_off_dJ(N, m, NB, nblk, Nt, S, W, RB) + (size_t)Nt * nu) * sizeof(double);
 }
+// the most LDS a launch may take (dynamic plus the kernel's static share): the shape falls back or the eval declines
+constexpr size_t BLKSEG_LDS_MAX = (size_t)160 * 1024;
 // slice-steps whose block sums are reduced together (phase 3): as many as the reducing lanes of one wave allow
 // (RB x segments per wave x controls <= 64), at most 4
 __host__ __device__ inline int blkseg_rb(int upw, int nu) {
@@ -589,34 +598,61 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
   double2* const slot = reinterpret_cast<double2*>(lds + blkseg_off_slot(NB, nblk, Nt));
   double2* const g0s = reinterpret_cast<double2*>(lds + blkseg_off_g0(NB, nblk, Nt, S));
   double* const xN = lds + blkseg_off_xN(NB, nblk, Nt, S);
+  double2* const xtl = reinterpret_cast<double2*>(lds + blkseg_off_xt(N, m, NB, nblk, Nt, S));
   cx<double>* const cf = reinterpret_cast<cx<double>*>(lds + blkseg_off_cf(N, m, NB, nblk, Nt, S));
   double* const red = lds + blkseg_off_red(N, m, NB, nblk, Nt, S);
   double* const wred = lds + blkseg_off_wred(N, m, NB, nblk, Nt, S);
   const int RB = sp.RB;
   double* const dJ = lds + blkseg_off_dJ(N, m, NB, nblk, Nt, S, W, RB);
 
-  // ---- prologue: generator blocks, x_0, the seed's largest ρ_k ----
+  // ---- the lane's unit: block beta of segment s = w UPW + uw ----
+  const int uw = l / nblk;
+  const bool lact = uw < sp.UPW;
+  const int beta = lact ? l - uw * nblk : 0;
+  // ---- prologue: generator blocks, x_0, X_target, the seed's largest ρ_k ----
+  // Every global read of the prologue is issued before the first wait, so that they share one round trip instead of
+  // four in a row: each thread's first entry of the packed generator table, of x_0 and of X_target, the rows of its
+  // lane's block and its first two slices of u (at cavity size that is all there is); then the LDS stores, and what
+  // longer arrays have left in plain loops.
+  const int ntab = 3 * E * nblk;
+  const double2* const x0g = reinterpret_cast<const double2*>(g.x0) + (g.x0_per_seed ? (size_t)b * Nm : 0);
+  const double2* const xtg = reinterpret_cast<const double2*>(g.Xt);
+  const double* ub = sp.u + (size_t)b * Nt * nu;
+  // two controls in an aligned buffer: one 16-byte load per slice
+  const bool u16 = nu == 2 && (reinterpret_cast<size_t>(ub) & 15) == 0;
+  auto load_u = [&](int k) -> double2 {
+    if (u16) return reinterpret_cast<const double2*>(ub)[k];
+    return make_double2(nu > 0 ? ub[(size_t)k * nu] : 0.0, nu > 1 ? ub[(size_t)k * nu + 1] : 0.0);
+  };
+  const bool hasx = MODE != BLKSEG_BWD && (size_t)tid < Nm;
+  double2 tab0 = make_double2(0.0, 0.0), x00 = tab0, xt0 = tab0, ua = tab0, ubb = tab0;
+  if (tid < ntab) tab0 = sp.gtab[tid];
+  if (hasx) {
+    x00 = x0g[tid];
+    xt0 = xtg[tid];
+  }
+  if (tid < Nt) ua = load_u(tid);
+  if (tid + nthr < Nt) ubb = load_u(tid + nthr);
+  int brw[NB];
+#pragma unroll
+  for (int i = 0; i < NB; ++i) brw[i] = bk.brow[beta * NB + i];
   {
-    const cx<double>* At = (const cx<double>*)g.At;
-    const size_t NN = (size_t)N * N;
-    for (int q = tid; q < 3 * E * nblk; q += nthr) {  // block-major [nblk][3][E]: compile-time offsets per block
-      const int beta = q / (3 * E), r = q - beta * 3 * E, j = r / E, e = r - j * E;
-      const int ri = bk.brow[beta * NB + e / NB], rk = bk.brow[beta * NB + e % NB];
-      cx<double> v = {0.0, 0.0};
-      if (j <= nu && ri >= 0 && rk >= 0) v = At[(size_t)j * NN + ri + (size_t)N * rk];
-      gsh[q] = make_double2(v.r, v.i);
-    }
+    if (tid < ntab) gsh[tid] = tab0;
+    for (int q = tid + nthr; q < ntab; q += nthr) gsh[q] = sp.gtab[q];
     if constexpr (MODE != BLKSEG_BWD) {
-      const cx<double>* x0 = (const cx<double>*)g.x0 + (g.x0_per_seed ? (size_t)b * Nm : 0);
-      for (size_t o = tid; o < Nm; o += nthr) {
-        xN[2 * o] = x0[o].r;
-        xN[2 * o + 1] = x0[o].i;
+      double2* const xN2 = reinterpret_cast<double2*>(xN);
+      if (hasx) {
+        xN2[tid] = x00;
+        xtl[tid] = xt0;
+      }
+      for (size_t o = (size_t)tid + nthr; o < Nm; o += nthr) {
+        xN2[o] = x0g[o];
+        xtl[o] = xtg[o];
       }
     }
   }
   // one pass over u: ρ_k, the copies of u (the stale check, the lazy rebuilds) and the records
   // [Re e^{μ_k}, Im e^{μ_k}, u_1k, u_2k] (e^{μ_k} does not depend on J; u is scaled by 2^-J below when J > 0)
-  const double* ub = sp.u + (size_t)b * Nt * nu;
   double rmax = 0.0;
   // controls without shifts: e^{μ_k} = e^{μ_0} in every slice (the same value), one exp and sincos per thread
   const bool cmu = sp.mur[1] == 0.0 && sp.mur[2] == 0.0 && sp.mui[1] == 0.0 && sp.mui[2] == 0.0;
@@ -627,8 +663,8 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
     sincos(sp.mui[0], &sn, &cs);
     emu0 = make_double2(er * cs, er * sn);
   }
-  for (int k = tid; k < Nt; k += nthr) {
-    const double u1 = nu > 0 ? ub[(size_t)k * nu] : 0.0, u2 = nu > 1 ? ub[(size_t)k * nu + 1] : 0.0;
+  auto slice = [&](int k, double2 uk) {
+    const double u1 = uk.x, u2 = uk.y;
     for (int j = 0; j < nu; ++j) {
       const double v = j ? u2 : u1;
       if (sp.u_copy) sp.u_copy[((size_t)b * Nt + k) * nu + j] = v;
@@ -647,7 +683,10 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
       r[0] = make_double2(er * cs, er * sn);
     }
     r[1] = make_double2(u1, u2);
-  }
+  };
+  if (tid < Nt) slice(tid, ua);
+  if (tid + nthr < Nt) slice(tid + nthr, ubb);
+  for (int k = tid + 2 * nthr; k < Nt; k += nthr) slice(k, load_u(k));
   rmax = block_max(rmax, red);  // (its barriers also publish the records)
   // J: the fewest halvings with ρ / 2^J <= θ_cap; P: the smallest degree whose tail bound
   // b^{P+1} / (P+1)! / (1 - b / (P+2)) is <= 2^-53 (b = ρmax / 2^J; every slice's ρ_k is <= ρmax)
@@ -682,17 +721,10 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
   BK_T(t1);
   BK_ADD(0, t1 - t0);
 
-  // ---- the lane's unit: segment s, block beta ----
-  const int uw = l / nblk;
-  const bool lact = uw < sp.UPW;
-  const int beta = lact ? l - uw * nblk : 0;
   const int s = w * sp.UPW + uw;
   const bool sact = lact && s < S;
   const int kb = sact ? s * L : 0;
   const int ke = sact ? min(kb + L, Nt) : 0;
-  int brw[NB];
-#pragma unroll
-  for (int i = 0; i < NB; ++i) brw[i] = bk.brow[beta * NB + i];
   double2 greg[GREG ? 3 : 1][GREG ? E : 1];
   if constexpr (GREG) {
 #pragma unroll
@@ -937,7 +969,7 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
   }
   __syncthreads();
   // J and the λ_N coefficients (src/penalty_fcns.jl:15-42)
-  chain_costs<double>(N, m, (const cx<double>*)g.Xt, [&](int q) { return cx<double>{xN[2 * q], xN[2 * q + 1]}; },
+  chain_costs<double>(N, m, reinterpret_cast<const cx<double>*>(xtl), [&](int q) { return cx<double>{xN[2 * q], xN[2 * q + 1]}; },
                       g.cost_kind, g.n_norm, 0.0, red, red + 16, cf, g.sc);
   __syncthreads();
   if (tid < 2 * m) {
@@ -1013,7 +1045,7 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
   if (early) publish();
   // G_N = Σ_c x_N λ_N^H on each block, G_0 = Q_{S-1}^H G_N Q_{S-1}
   if (last) {
-    const cx<double>* Xt = (const cx<double>*)g.Xt;
+    const cx<double>* Xt = reinterpret_cast<const cx<double>*>(xtl);  // (the prologue's LDS copy)
     double gr[E], gi[E];
 #pragma unroll
     for (int e = 0; e < E; ++e) gr[e] = gi[e] = 0.0;

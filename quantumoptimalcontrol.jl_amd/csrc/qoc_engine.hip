@@ -168,8 +168,10 @@ hipEvent_t take_event(qoc_ctx* c) {
     c->event_pool.pop_back();
     return e;
   }
+  // timing only: nothing on the host reads what the kernels wrote on the strength of these events, so their records
+  // need no system-scope fence (a plain event's record writes back everything the launch before it left dirty)
   hipEvent_t e = nullptr;
-  (void)hipEventCreate(&e);
+  (void)hipEventCreateWithFlags(&e, hipEventDisableSystemFence);
   return e;
 }
 
@@ -551,6 +553,7 @@ void qoc_destroy(qoc_ctx* c) {
   if (c->d_tcoef) hipFree(c->d_tcoef);
   if (c->d_coef_mu) hipFree(c->d_coef_mu);
   if (c->d_brow) hipFree(c->d_brow);
+  if (c->d_gtab) hipFree(c->d_gtab);
   if (c->d_wrow) hipFree(c->d_wrow);
   if (c->d_wrow_live) hipFree(c->d_wrow_live);
   if (c->d_dead_rows) hipFree(c->d_dead_rows);

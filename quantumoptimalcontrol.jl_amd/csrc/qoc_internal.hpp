@@ -31,6 +31,12 @@
 
 using namespace qoc;
 
+// launch shape of the segmented block eval (qoc_run_blk.hip blkseg_shape)
+struct BlksegShape {
+  int W, S, L, UPW, RB;
+  size_t lds;
+};
+
 struct qoc_ctx {
   int dev = 0, N = 0, m = 0, nu = 0, Nt = 0, B = 0, prec = QOC_FP64;
   size_t esz = 16;  // bytes per complex element on device
@@ -193,6 +199,13 @@ struct qoc_ctx {
   int fwd_kind = 0;
   double2* d_gseg = nullptr;         // B x NB^2 x S x nblk complex
   size_t gseg_bytes = 0;
+  // the segmented eval's launch shape, kept between evals: valid while the sizes it was derived from (seg_key: B, Nt,
+  // N, m, nu, block rows, blocks) are the context's; the QOC_BLKSEG_W / _S / _RB switches are read when it is
+  // derived.  seg_attr[NB - 2][order - 1][mode]: this context has raised that k_blkseg_eval instance's dynamic-LDS
+  // limit (blkseg_lds_attr)
+  mutable BlksegShape seg_shape{};
+  mutable int seg_key[7] = {-1, -1, -1, -1, -1, -1, -1};
+  bool seg_attr[2][4][3] = {};
   int* h_flag = nullptr;             // host-mapped stale-u flag of the queued check (k_compare_u_flags)
   int flag_turn = 0;                 // which of the two device flags d_flag[0 / 1] the next queued check writes
   hipEvent_t flag_ev = nullptr;      // recorded after that copy
@@ -210,6 +223,7 @@ struct qoc_ctx {
   int blk_nb = 0;                // padded block size 2 / 3 / 4 (VALU lanes), 16 (MFMA block waves), 0: no block path
   int nblk = 0;                  // blocks
   int* d_brow = nullptr;         // nblk x blk_nb rows of each block (-1 padding)
+  double2* d_gtab = nullptr;     // blocks of <= 3 rows: [nblk][3][blk_nb^2] shifted generator blocks (blk_detect)
   int blk_jr = 0;                // chain kernels: 0 VALU lanes (k_blk_*), 1 / 4 MFMA block waves (k_blkrot_*<JR>)
   bool blk_real = false;         // MFMA block waves on the real embedding of blocks of <= 2 rows (k_blkrot_*<0>)
   int nwb = 0;                   // MFMA block waves per column pair

@@ -126,6 +126,30 @@ int blk_detect(qoc_ctx* c) {
   HIPCHK(c, hipMalloc((void**)&c->d_brow, brow.size() * sizeof(int)));
   HIPCHK(c, hipMemcpy(c->d_brow, brow.data(), brow.size() * sizeof(int), hipMemcpyHostToDevice));
   c->blk_dev_bytes += brow.size() * sizeof(int);
+  if (c->d_gtab) {
+    HIPCHK(c, hipFree(c->d_gtab));
+    c->d_gtab = nullptr;
+  }
+  if (NB <= 3) {
+    // the segmented eval's generator blocks, block-major [nblk][3][NB^2]: the entries of the shifted generators
+    // Ã_j = A_j - μ_j I (the values qoc_set_generators uploads to d_At: the same subtraction) on each block's rows,
+    // zero for j > nu and for a padded row; its prologue copies the table instead of gathering through d_brow
+    const int E = NB * NB;
+    std::vector<double> tab((size_t)nblk * 3 * E * 2, 0.0);
+    for (int b = 0; b < nblk; ++b)
+      for (int j = 0; j <= c->nu && j < 3; ++j)
+        for (int e = 0; e < E; ++e) {
+          const int ri = brow[(size_t)b * NB + e / NB], rk = brow[(size_t)b * NB + e % NB];
+          if (ri < 0 || rk < 0) continue;
+          const double* v = c->h_gen.data() + 2 * (j * NN + ri + (size_t)N * rk);
+          double* t = tab.data() + 2 * (((size_t)b * 3 + j) * E + e);
+          t[0] = ri == rk ? v[0] - c->tprm.mur[j] : v[0];
+          t[1] = ri == rk ? v[1] - c->tprm.mui[j] : v[1];
+        }
+    HIPCHK(c, hipMalloc((void**)&c->d_gtab, tab.size() * sizeof(double)));
+    HIPCHK(c, hipMemcpy(c->d_gtab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
+    c->blk_dev_bytes += tab.size() * sizeof(double);
+  }
   if (jr || real) {
     HIPCHK(c, hipMalloc((void**)&c->d_wrow, wrow.size() * sizeof(int)));
     HIPCHK(c, hipMemcpy(c->d_wrow, wrow.data(), wrow.size() * sizeof(int), hipMemcpyHostToDevice));
@@ -1651,15 +1675,20 @@ static int blku_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu) {
 }
 
 // ---- segmented block eval (qoc_blkseg.hpp) -------------------------------------------------------------------------
-struct BlksegShape {
-  int W, S, L, UPW, RB;
-  size_t lds;
-};
 // One workgroup per seed with W waves (8 at one seed per CU, fewer when several seeds share a CU: 8 wave slots at the
 // kernel's <= 256 VGPRs), UPW = 64 / nblk segments per wave, S = W UPW segments of L = ceil(Nt / S) slices (then S
 // trimmed so that no segment is empty).  QOC_BLKSEG_W / QOC_BLKSEG_S override the waves / cap the segments.
-static BlksegShape blkseg_shape(const qoc_ctx* c) {
-  BlksegShape s{};
+// Derived once per context and again when one of its inputs changes (qoc_ctx::seg_key): every eval asks for it, some
+// twice, and the B = 1 plumbing latency is host time.  The sizes are compared here, not invalidated by their setters:
+// m moves with the state packing and the blocks with every qoc_set_generators, and a missed setter would launch a
+// stale shape.  The cache is the context's (mutable members: blkseg_ok, a predicate on a const context, fills it
+// too); like the rest of a context it is for one host thread at a time.  The reference returned stays valid until
+// the next call with other sizes.
+static const BlksegShape& blkseg_shape(const qoc_ctx* c) {
+  const int key[7] = {c->B, c->Nt, c->N, c->m, c->nu, c->blk_nb, c->nblk};
+  if (std::equal(key, key + 7, c->seg_key)) return c->seg_shape;
+  BlksegShape& s = c->seg_shape;
+  s = BlksegShape{};
   const int per_cu = std::max(1, std::min(8, (c->B + c->ncu - 1) / std::max(1, c->ncu)));
   s.W = std::max(1, 8 / per_cu);
   if (const char* env = getenv("QOC_BLKSEG_W")) s.W = std::max(1, std::min(8, atoi(env)));
@@ -1675,10 +1704,11 @@ static BlksegShape blkseg_shape(const qoc_ctx* c) {
   const int rbmax = std::max(1, 64 / (s.UPW * std::max(1, c->nu)));
   if (c->blk_nb == 2) {
     const int rb8 = std::min(8, rbmax);
-    if (blkseg_lds(c->N, c->m, c->nu, c->blk_nb, c->nblk, c->Nt, s.S, s.W, rb8) <= (size_t)160 * 1024) s.RB = rb8;
+    if (blkseg_lds(c->N, c->m, c->nu, c->blk_nb, c->nblk, c->Nt, s.S, s.W, rb8) <= BLKSEG_LDS_MAX) s.RB = rb8;
   }
   if (const char* e = getenv("QOC_BLKSEG_RB")) s.RB = std::max(1, std::min(atoi(e), rbmax));
   s.lds = blkseg_lds(c->N, c->m, c->nu, c->blk_nb, c->nblk, c->Nt, s.S, s.W, s.RB);
+  std::copy(key, key + 7, c->seg_key);
   return s;
 }
 
@@ -1691,7 +1721,7 @@ bool blkseg_ok(const qoc_ctx* c, int order) {
   if (c->cost_kind != QOC_COST_TRACE && c->cost_kind != QOC_COST_ZCAL) return false;
   const char* env = getenv("QOC_BLKSEG");
   if (env && !std::strcmp(env, "0")) return false;
-  return blkseg_shape(c).lds <= (size_t)160 * 1024;
+  return blkseg_shape(c).lds <= BLKSEG_LDS_MAX;
 }
 
 template <typename F>
@@ -1726,6 +1756,7 @@ static int blkseg_params(qoc_ctx* c, const BlksegShape& s, BlksegParams& sp) {
   sp.L = s.L;
   sp.UPW = s.UPW;
   sp.RB = s.RB;
+  sp.gtab = c->d_gtab;
   sp.terms = c->d_terms;
   // the best (J, seed) for qoc_allgather_best_dev, found by the launch's last workgroup
   if (!c->d_best) {  // no communicator yet: this context alone (the epilogue's own layout)
@@ -1748,6 +1779,21 @@ static int blkseg_params(qoc_ctx* c, const BlksegShape& s, BlksegParams& sp) {
   return QOC_OK;
 }
 
+// blk_lds_attr for the segmented eval's kernels without a runtime call per launch: a context sets a kernel's limit
+// once (seg_attr), to the most the eval ever asks for (BLKSEG_LDS_MAX less the kernel's static LDS) and not to its own
+// size, because the limit belongs to the kernel, not to the context: another context with a smaller shape must not
+// lower it
+static hipError_t blkseg_lds_attr(qoc_ctx* c, int nb, int ord, int mode, const void* kern, size_t lds) {
+  bool& set = c->seg_attr[nb - 2][ord - 1][mode];
+  if (lds <= 65536 || set) return hipSuccess;
+  hipFuncAttributes fa{};
+  hipError_t e = hipFuncGetAttributes(&fa, kern);
+  if (e != hipSuccess) return e;
+  e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BLKSEG_LDS_MAX - fa.sharedSizeBytes));
+  set = e == hipSuccess;
+  return e;
+}
+
 template <int MODE>
 static hipError_t blkseg_launch(qoc_ctx* c, int order, const BlksegShape& s, const BlksegParams& sp) {
   const TChainArgs g = tchain_args(c);
@@ -1759,7 +1805,7 @@ static hipError_t blkseg_launch(qoc_ctx* c, int order, const BlksegShape& s, con
       return hipErrorInvalidValue;
     } else {
       auto kern = k_blkseg_eval<NB, ORD, 8, MODE>;
-      const hipError_t q = blk_lds_attr(kern, s.lds);
+      const hipError_t q = blkseg_lds_attr(c, NB, ORD, MODE, (const void*)kern, s.lds);
       if (q != hipSuccess) return q;
       hipLaunchKernelGGL(kern, dim3(c->B), dim3(64 * s.W), s.lds, c->stream, g, bk, sp);
       return hipGetLastError();

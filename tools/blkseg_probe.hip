@@ -50,6 +50,17 @@ void run(int B, int Nt, int nblk, int m, int W, int Scap, int noturn = 0, int tu
   (void)hipMemcpy(du, u.data(), u.size() * 8, hipMemcpyHostToDevice);
   (void)hipMemcpy(dx0, x0.data(), x0.size() * 16, hipMemcpyHostToDevice);
   (void)hipMemcpy(dbrow, brow.data(), brow.size() * 4, hipMemcpyHostToDevice);
+  // the packed generator table [nblk][3][NB^2] (BlksegParams::gtab; no shifts here, so the generators' own entries)
+  std::vector<double2> tab((size_t)nblk * 3 * NB * NB);
+  for (int b = 0; b < nblk; ++b)
+    for (int j = 0; j < 3; ++j)
+      for (int e = 0; e < NB * NB; ++e) {
+        const cx<double> v = A[j * NN + brow[b * NB + e / NB] + (size_t)N * brow[b * NB + e % NB]];
+        tab[((size_t)b * 3 + j) * NB * NB + e] = make_double2(v.r, v.i);
+      }
+  double2* dtab;
+  (void)hipMalloc(&dtab, tab.size() * 16);
+  (void)hipMemcpy(dtab, tab.data(), tab.size() * 16, hipMemcpyHostToDevice);
   TChainArgs g{};
   g.N = N; g.m = m; g.nu = nu; g.Nt = Nt; g.At = dA; g.u = du; g.x0 = dx0;
   g.Xt = dx0; g.cost_kind = COST_TRACE; g.n_norm = m; g.J = dJ; g.coef = dcoef;
@@ -66,6 +77,7 @@ void run(int B, int Nt, int nblk, int m, int W, int Scap, int noturn = 0, int tu
   sp.RB = blkseg_rb(sp.UPW, nu);
   sp.u = du;
   sp.dJdu = ddJ;
+  sp.gtab = dtab;
   const size_t lds = blkseg_lds(N, m, nu, NB, nblk, Nt, sp.S, W, sp.RB);
   if (lds > 160 * 1024) return;
   (void)hipFuncSetAttribute((const void*)k_blkseg_eval<NB, 3, WMAX>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -102,7 +114,7 @@ void run(int B, int Nt, int nblk, int m, int W, int Scap, int noturn = 0, int tu
   for (int w = 0; w < W; ++w) printf(" %7llu", sw[16 + w]);
   printf("\n");
   (void)hipFree(dA); (void)hipFree(du); (void)hipFree(dx0); (void)hipFree(dcoef); (void)hipFree(dJ);
-  (void)hipFree(ddJ); (void)hipFree(dbrow);
+  (void)hipFree(ddJ); (void)hipFree(dbrow); (void)hipFree(dtab);
 }
 
 int main(int argc, char** argv) {
