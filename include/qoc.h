@@ -65,7 +65,12 @@ int qoc_set_x0(qoc_ctx* ctx, const double* x0, int per_seed);
 /* Terminal cost: kind QOC_COST_TRACE (X_target N x m, normalisation n),
  * QOC_COST_ZCAL (m must be 4; every propagation path), QOC_COST_EXTERNAL (X_target may be NULL). */
 int qoc_set_cost(qoc_ctx* ctx, int kind, const double* X_target, double n);
-/* Guard-state penalty L = mu sum |x[P,C]|^2 (src/penalty_fcns.jl:1-11); 0-based indices; mu = 0 disables. */
+/* Guard-state penalty L = mu sum |x[P,C]|^2 (src/penalty_fcns.jl:1-11), summed over the Nt + 1 states in J and added
+ * as 2 mu x_k[P,C] to every co-state; 0-based indices; mu = 0 (or an empty P or C) disables.  Generators with
+ * invariant blocks of 2-3 rows keep the one-launch segmented eval and its split form with the penalty set
+ * (QOC_BLKSEG_PEN=0: the block chains instead); a co-state source (qoc_set_costate_source) takes the chains.  May be
+ * called on a live context: lazily kept states / co-states are materialised first, and a propagate made before the
+ * call is followed by a grape_sensitivity on rebuilt states. */
 int qoc_set_state_penalty(qoc_ctx* ctx, const int* P, int np, const int* C, int nc, double mu);
 
 /* propagate (src/gradient_computations.jl:2-32) for all B seeds, host pointers.

@@ -28,6 +28,27 @@
 // phase 2 (BLKSEG_FWD: phases 0-2, which also write G at every segment's end, Q_s G_0 Q_s^H, to HBM: S nblk NB^2
 // complex per seed, 31 KB at cavity size) and BLKSEG_BWD (phase 0's records and (J, P) again -- the same arithmetic on
 // the same u, so the same values -- then phase 3 from those G): bitwise the fused launch's J and dJdu.
+//
+// The guard-state penalty (the PEN instantiations; setup_state_penalty, src/penalty_fcns.jl:1-11, consumed at
+// src/gradient_computations.jl:47-49,55-57): L(x) = μ Σ_{i in P, c in C} |x_ic|^2 on all Nt + 1 states, and the source
+// 2 μ x_k[P, C] of every λ_k.  No state comes back for it.  Per block, with Π the 0/1 projector on its rows in P,
+// D_k = Σ_{c in C} x_k,c x_k,c^H and W_k = U_{k-1} .. U_0 (unitary): D_k = W_k D_0 W_k^H moves by the same
+// conjugation as G, G_k = K_k U_k + 2 μ D_k Π, and with R_k = W_k^H Π W_k the frame of time 0 has
+// W_k^H (K_k U_k) W_k = G~_N,cost + 2 μ D_0 Σ_{j > k} R_j and Σ_k L(x_k) = μ tr(D_0 Σ_{k=0}^{Nt} R_k).
+//   phase 1  beside P_s, H_s = Σ V^H Π V over the running product V after each slice (one outer product per
+//            penalised row), then H'_s = P_s H_s P_s^H;
+//   phase 2  T_s = Q_s^H H'_s Q_s = Σ_{k in (kb, ke]} R_k; suffix sums of T over the segments (additions only: a scan
+//            inside each wave through the lanes' rows of the segment products' area, then the later waves' totals);
+//            D_0 from x_0 before x_N overwrites it; J += μ Σ_blocks Re tr(D_0 (Π + Σ_s T_s)) before J is published;
+//            at the segment's end G = Q_s (G_0 + 2 μ D_0 Σ_{s' > s} T_s') Q_s^H (without the end's own source) and
+//            D = Q_s D_0 Q_s^H;
+//   phase 3  per slice G += 2 μ D Π (the source of λ_{k+1}), D <- U_k^H D U_k, then K_k and G_k as before.  D lives
+//            in the lane's own row of the segment products' area (free by then), not in registers.
+// BLKSEG_FWD also writes D at the segment ends (dseg, behind gseg).  The λ_N coefficients stay the cost's alone; the
+// co-states' rebuild (blku_costates) adds the sources from rebuilt states.  Lanes of blocks without a row in P skip
+// all of it (uniform control flow apart).  Extra LDS: D_0 per block.  Blocks of 3 rows: the fused penalised kernel
+// does not fit 256 VGPRs (it spills), so the host runs the penalised eval as BLKSEG_FWD + BLKSEG_BWD, which do
+// (qoc_run_blk.hip blkseg_eval), and BLKSEG_FUSED with PEN is built for blocks of 2 rows only.
 #pragma once
 #include "qoc_blku.hpp"
 
@@ -64,13 +85,21 @@ struct BlksegParams {
   // the shifted generators' blocks, block-major [nblk][3][NB^2] (zeros for j > nu and for a padded row): built by the
   // host where the block layout and the shifted generators are established, copied to LDS by the prologue
   const double2* gtab;
+  // the guard-state penalty (PEN instantiations; setup_state_penalty, src/penalty_fcns.jl:1-11): L(x) = pen_mu
+  // Σ_{i in P, c in C} |x_ic|^2 summed over the Nt + 1 states.  prow[i]: bit β set when row i of block β is in P (never
+  // a padding row); pcol: bit c set when column c is in C; dseg: D = Σ_{c in C} x_c x_c^H per block at every segment's
+  // end, laid out like gseg (written by BLKSEG_FWD, read by BLKSEG_BWD)
+  double pen_mu;
+  unsigned int prow[3];
+  unsigned int pcol;
+  double2* dseg;
 };
 enum { BLKSEG_FUSED = 0, BLKSEG_FWD = 1, BLKSEG_BWD = 2 };
 
 // LDS, in doubles: shifted generator blocks [nblk][3][E] complex | step records [Nt][4] | segment products [S][E][nblk]
 // complex | G_0 [E][nblk] complex | x_0 then x_N (N m complex) | X_target (N m complex) | λ_N coefficients (2 m
 // complex) | scratch (24) |
-// per-wave partial sums [W][RB][64][2] | dJdu [Nt][nu]
+// per-wave partial sums [W][RB][64][2] | dJdu [Nt][nu] | penalised shapes: D_0 [E][nblk] complex
 __host__ __device__ inline size_t blkseg_off_rec(int NB, int nblk) { return (size_t)6 * NB * NB * nblk; }
 __host__ __device__ inline size_t blkseg_off_slot(int NB, int nblk, int Nt) { return blkseg_off_rec(NB, nblk) + 4 * (size_t)Nt; }
 __host__ __device__ inline size_t blkseg_off_g0(int NB, int nblk, int Nt, int S) {
@@ -94,7 +123,13 @@ __host__ __device__ inline size_t blkseg_off_wred(int N, int m, int NB, int nblk
 __host__ __device__ inline size_t blkseg_off_dJ(int N, int m, int NB, int nblk, int Nt, int S, int W, int RB) {
   return blkseg_off_wred(N, m, NB, nblk, Nt, S) + (size_t)128 * W * RB;
 }
-__host__ __device__ inline size_t blkseg_lds(int N, int m, int nu, int NB, int nblk, int Nt, int S, int W, int RB) {
+// (D_0 starts on a 16-byte boundary)
+__host__ __device__ inline size_t blkseg_off_d0(int N, int m, int nu, int NB, int nblk, int Nt, int S, int W, int RB) {
+  return (blkseg_off_dJ(N, m, NB, nblk, Nt, S, W, RB) + (size_t)Nt * nu + 1) & ~(size_t)1;
+}
+__host__ __device__ inline size_t blkseg_lds(int N, int m, int nu, int NB, int nblk, int Nt, int S, int W, int RB,
+                                             bool pen = false) {
+  if (pen) return (blkseg_off_d0(N, m, nu, NB, nblk, Nt, S, W, RB) + (size_t)2 * NB * NB * nblk) * sizeof(double);
   return (blkseg_off_dJ(N, m, NB, nblk, Nt, S, W, RB) + (size_t)Nt * nu) * sizeof(double);
 }
 // the most LDS a launch may take (dynamic plus the kernel's static share): the shape falls back or the eval declines
@@ -572,10 +607,72 @@ struct SegProg {
   }
 };
 
+// ---- the guard-state penalty (PEN) ----
+// H += Σ_{i in pm} v_i^H v_i over the penalised rows v_i of the running product V (V^H Π V, Π the block's projector)
+template <int NB>
+__device__ __forceinline__ void seg_pen_acc(int pm, const double (&vr)[NB * NB], const double (&vi)[NB * NB],
+                                            double (&hr)[NB * NB], double (&hi)[NB * NB]) {
+#pragma unroll
+  for (int i = 0; i < NB; ++i)
+    if ((pm >> i) & 1) {
+#pragma unroll
+      for (int a = 0; a < NB; ++a)
+#pragma unroll
+        for (int q = 0; q < NB; ++q) {
+          const double ar = vr[i * NB + a], ai = vi[i * NB + a], br = vr[i * NB + q], bi = vi[i * NB + q];
+          hr[a * NB + q] = fma(ar, br, fma(ai, bi, hr[a * NB + q]));
+          hi[a * NB + q] = fma(ar, bi, fma(-ai, br, hi[a * NB + q]));
+        }
+    }
+}
+// One slice of the penalty in phase 3, D in LDS (entry e at dp[e stride]): G += f D Π on the penalised columns of D
+// (the source 2 μ x_k[P, C] of λ_k in G_k = Σ_c x_k λ_k^H), then D <- U^H D U.  D is read column by column (T = D U
+// accumulated) and written back row by row (U^H T), so that beside U and G only T is live.
+template <int NB>
+__device__ __forceinline__ void seg_pen_step(int pm, double f, double2* dp, int stride, const double (&ur)[NB * NB],
+                                             const double (&ui)[NB * NB], double (&gr)[NB * NB], double (&gi)[NB * NB]) {
+  double tr[NB * NB], ti[NB * NB];
+#pragma unroll
+  for (int e = 0; e < NB * NB; ++e) tr[e] = ti[e] = 0.0;
+#pragma unroll
+  for (int q = 0; q < NB; ++q) {
+    double2 c[NB];
+#pragma unroll
+    for (int a = 0; a < NB; ++a) c[a] = dp[(a * NB + q) * stride];
+    if ((pm >> q) & 1) {
+#pragma unroll
+      for (int a = 0; a < NB; ++a) {
+        gr[a * NB + q] = fma(f, c[a].x, gr[a * NB + q]);
+        gi[a * NB + q] = fma(f, c[a].y, gi[a * NB + q]);
+      }
+    }
+#pragma unroll
+    for (int a = 0; a < NB; ++a)
+#pragma unroll
+      for (int j = 0; j < NB; ++j) {
+        tr[a * NB + j] = fma(c[a].x, ur[q * NB + j], fma(-c[a].y, ui[q * NB + j], tr[a * NB + j]));
+        ti[a * NB + j] = fma(c[a].x, ui[q * NB + j], fma(c[a].y, ur[q * NB + j], ti[a * NB + j]));
+      }
+  }
+#pragma unroll
+  for (int i = 0; i < NB; ++i)
+#pragma unroll
+    for (int j = 0; j < NB; ++j) {
+      double sr = 0.0, si = 0.0;
+#pragma unroll
+      for (int q = 0; q < NB; ++q) {
+        sr = fma(ur[q * NB + i], tr[q * NB + j], fma(ui[q * NB + i], ti[q * NB + j], sr));
+        si = fma(ur[q * NB + i], ti[q * NB + j], fma(-ui[q * NB + i], tr[q * NB + j], si));
+      }
+      dp[(i * NB + j) * stride] = make_double2(sr, si);
+    }
+}
+
 // One workgroup per seed (blockIdx.x), W = blockDim / 64 waves, UPW segments of nblk lanes per wave (lanes past
-// UPW nblk idle).  Built-in costs only (TRACE / ZCAL), no state penalty, no co-state source, unpacked states,
-// skew-Hermitian generators (the host's blkseg_ok).
-template <int NB, int ORD, int WMAX, int MODE = BLKSEG_FUSED>
+// UPW nblk idle).  Built-in costs only (TRACE / ZCAL), no co-state source, unpacked states, skew-Hermitian generators
+// (the host's blkseg_ok).  PEN: with the state penalty on the rows P and columns C of sp.prow / sp.pcol (the header
+// comment's penalty section); PEN = false is the unpenalised kernel, instruction for instruction.
+template <int NB, int ORD, int WMAX, int MODE = BLKSEG_FUSED, bool PEN = false>
 __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, const BlkArgs bk, const BlksegParams sp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   if constexpr (MODE == BLKSEG_BWD) {  // a stale u (the check queued before this launch): leave every output alone
@@ -604,11 +701,21 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
   double* const wred = lds + blkseg_off_wred(N, m, NB, nblk, Nt, S);
   const int RB = sp.RB;
   double* const dJ = lds + blkseg_off_dJ(N, m, NB, nblk, Nt, S, W, RB);
+  double2* const d0s = reinterpret_cast<double2*>(lds + blkseg_off_d0(N, m, nu, NB, nblk, Nt, S, W, RB));  // (PEN)
 
   // ---- the lane's unit: block beta of segment s = w UPW + uw ----
   const int uw = l / nblk;
   const bool lact = uw < sp.UPW;
   const int beta = lact ? l - uw * nblk : 0;
+  // PEN: the penalised rows of the lane's block (bit i: row i), 0 for lanes without a segment; lanes of blocks without
+  // a penalised row skip all of the penalty's arithmetic
+  int pm = 0;
+  if constexpr (PEN) {
+    if (lact && w * sp.UPW + uw < S)
+#pragma unroll
+      for (int i = 0; i < NB; ++i) pm |= (int)((sp.prow[i] >> beta) & 1u) << i;
+  }
+  constexpr int PE = PEN ? NB * NB : 1;
   // ---- prologue: generator blocks, x_0, X_target, the seed's largest ρ_k ----
   // Every global read of the prologue is issued before the first wait, so that they share one round trip instead of
   // four in a row: each thread's first entry of the packed generator table, of x_0 and of X_target, the rows of its
@@ -761,6 +868,11 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
     qr[e] = e % (NB + 1) == 0 ? 1.0 : 0.0;
     qi[e] = 0.0;
   }
+  // PEN: H_s = Σ V^H Π V over the running product V after each slice of the segment (the states x_{kb+1} .. x_{ke} in
+  // the frame of the segment's start); later T_s, its suffix sums and X_s (phase 2)
+  double Hr[PE], Hi[PE];
+#pragma unroll
+  for (int e = 0; e < PE; ++e) Hr[e] = Hi[e] = 0.0;
   // every segment but the last has L slices; below Lf (the last one's length) no lane of a segment is past its end,
   // so those steps need no selects
   const int Lf = Nt - (S - 1) * L;
@@ -806,6 +918,9 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
           qr[e] = !SEL || act[v] ? tr[e] : qr[e];
           qi[e] = !SEL || act[v] ? ti[e] : qi[e];
         }
+        if constexpr (PEN) {
+          if (pm && (!SEL || act[v])) seg_pen_acc<NB>(pm, qr, qi, Hr, Hi);
+        }
       }
     }
   };
@@ -829,12 +944,21 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
   // G at the end of the lane's segment (phase 3's start): formed here, or read back (BLKSEG_BWD)
   double Gr[E], Gi[E];
   auto gseg_at = [&](int e) -> double2& { return sp.gseg[(((size_t)b * E + e) * S + s) * nblk + beta]; };
+  // PEN: D at the lane's current slice (phase 3) lives in the lane's own row dl_at of the segment products' LDS area,
+  // which is free after phase 2: held in registers across the contraction it would not fit beside G, U and K
+  auto dl_at = [&](int e) -> double2& { return slot[((size_t)s * E + e) * nblk + beta]; };
+  auto dseg_at = [&](int e) -> double2& { return sp.dseg[(((size_t)b * E + e) * S + s) * nblk + beta]; };
   if constexpr (MODE == BLKSEG_BWD) {
 #pragma unroll
     for (int e = 0; e < E; ++e) {
       const double2 v = sact ? gseg_at(e) : make_double2(0.0, 0.0);
       Gr[e] = v.x;
       Gi[e] = v.y;
+    }
+    if constexpr (PEN) {
+      if (pm)
+#pragma unroll
+        for (int e = 0; e < E; ++e) dl_at(e) = dseg_at(e);
     }
     // the co-states' rebuild source (blku_costates): this u (copied in the prologue) and the forward's λ_N coefficients
     if (sp.coef2 && tid < 2 * m) sp.coef2[(size_t)b * 2 * m + tid] = g.coef[(size_t)b * 2 * m + tid];
@@ -866,7 +990,44 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
           qr[e] = act[v] ? tr[e] : qr[e];
           qi[e] = act[v] ? ti[e] : qi[e];
         }
+        if constexpr (PEN) {
+          if (pm && act[v]) seg_pen_acc<NB>(pm, qr, qi, Hr, Hi);
+        }
       }
+    }
+  }
+  if constexpr (PEN) {
+    if (pm) {  // to the frame of the segment's end, where the inclusive prefix Q_s applies: H' = P_s H_s P_s^H
+      double tr[E], ti[E];
+      seg_mm<NB, false, false>(qr, qi, Hr, Hi, tr, ti);
+      seg_mm<NB, false, true>(tr, ti, qr, qi, Hr, Hi);
+    }
+    // D_0 = Σ_{c in C} x_0,c x_0,c^H of every block (the first segment's lanes), before x_N overwrites x_0 (after the
+    // scan's workgroup barrier below)
+    if (w == 0 && l < nblk) {
+      double dr[E], di[E];
+#pragma unroll
+      for (int e = 0; e < E; ++e) dr[e] = di[e] = 0.0;
+      if (pm)
+        for (int c = 0; c < m; ++c) {
+          if (!((sp.pcol >> c) & 1u)) continue;
+          double xr[NB], xi[NB];
+#pragma unroll
+          for (int i = 0; i < NB; ++i) {
+            const size_t o = 2 * ((size_t)c * N + max(brw[i], 0));
+            xr[i] = brw[i] >= 0 ? xN[o] : 0.0;
+            xi[i] = brw[i] >= 0 ? xN[o + 1] : 0.0;
+          }
+#pragma unroll
+          for (int a = 0; a < NB; ++a)
+#pragma unroll
+            for (int q = 0; q < NB; ++q) {
+              dr[a * NB + q] = fma(xr[a], xr[q], fma(xi[a], xi[q], dr[a * NB + q]));
+              di[a * NB + q] = fma(xi[a], xr[q], fma(-xr[a], xi[q], di[a * NB + q]));
+            }
+        }
+#pragma unroll
+      for (int e = 0; e < E; ++e) d0s[e * nblk + beta] = make_double2(dr[e], di[e]);
     }
   }
 
@@ -940,6 +1101,13 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
       qi[e] = ci[e];
     }
   }
+  if constexpr (PEN) {
+    if (pm) {  // T_s = Q_s^H H'_s Q_s = Σ_{k in (kb, ke]} R_k, R_k = W_k^H Π W_k: the segment's sum in the frame of time 0
+      double tr[E], ti[E];
+      seg_mm<NB, true, false>(qr, qi, Hr, Hi, tr, ti);
+      seg_mm<NB, false, false>(tr, ti, qr, qi, Hr, Hi);
+    }
+  }
   // x_N = Q_{S-1} x_0 on each block (the last segment's lanes), in place in xN
   const bool last = sact && s == S - 1;
   if (last) {
@@ -968,6 +1136,34 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
     }
   }
   __syncthreads();
+  if constexpr (PEN) {
+    // inclusive suffix sums of T over the segments of each wave, through the lanes' own rows of the segment products'
+    // area (every wave is past its reads of the products: the barrier above); additions only, wave syncs only
+    if (pm)
+#pragma unroll
+      for (int e = 0; e < E; ++e) slot_at(s, e) = make_double2(Hr[e], Hi[e]);
+    wave_lds_sync();
+    for (int d = 1; d < UPW; d <<= 1) {
+      const bool take = pm && uw0 + d < UPW && s + d < S;
+      double tr[E], ti[E];
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const double2 v = take ? slot_at(s + d, e) : make_double2(0.0, 0.0);
+        tr[e] = v.x;
+        ti[e] = v.y;
+      }
+      wave_lds_sync();
+      if (take) {
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          Hr[e] += tr[e];
+          Hi[e] += ti[e];
+          slot_at(s, e) = make_double2(Hr[e], Hi[e]);
+        }
+      }
+      wave_lds_sync();
+    }
+  }
   // J and the λ_N coefficients (src/penalty_fcns.jl:15-42)
   chain_costs<double>(N, m, reinterpret_cast<const cx<double>*>(xtl), [&](int q) { return cx<double>{xN[2 * q], xN[2 * q + 1]}; },
                       g.cost_kind, g.n_norm, 0.0, red, red + 16, cf, g.sc);
@@ -976,12 +1172,53 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
     g.coef[(size_t)b * 2 * m + tid] = cf[tid];
     if (sp.coef2) sp.coef2[(size_t)b * 2 * m + tid] = cf[tid];
   }
+  // PEN: the sum over the later waves' totals (the suffix sums of their first segments), waves in order
+  auto later_waves = [&](double (&ar)[E], double (&ai)[E]) {
+#pragma unroll
+    for (int e = 0; e < E; ++e) ar[e] = ai[e] = 0.0;
+    for (int v = w + 1; v < W; ++v)
+#pragma unroll
+      for (int e = 0; e < E; ++e) {
+        const double2 x = slot_at(v * UPW, e);
+        ar[e] += x.x;
+        ai[e] += x.y;
+      }
+  };
+  if constexpr (PEN) {
+    // the first segment's lanes take their block's share of Σ_k L(x_k) / μ = Re tr(D_0 (Π + Σ_s T_s)) (Π: the state
+    // x_0 itself); Σ_s T_s = the lane's own suffix sum (read back from its row: H is not kept in registers) plus the
+    // later waves' totals
+    double pj = 0.0;
+    if (pm && s == 0) {
+      double ar[E], ai[E];
+      later_waves(ar, ai);
+#pragma unroll
+      for (int a = 0; a < NB; ++a)
+#pragma unroll
+        for (int q = 0; q < NB; ++q) {
+          const double2 d0 = d0s[(a * NB + q) * nblk + beta], h = slot_at(0, q * NB + a);
+          const double mr = h.x + ar[q * NB + a] + (a == q && ((pm >> a) & 1) ? 1.0 : 0.0);
+          const double mi = h.y + ai[q * NB + a];
+          pj = fma(d0.x, mr, fma(-d0.y, mi, pj));
+        }
+    }
+    if (w == 0) {  // the blocks' shares to the first thread, summed there in block order
+      if (l < nblk) wred[l] = pj;
+      wave_lds_sync();
+    }
+  }
   if (tid == 0) {
+    double Jv = red[16];
+    if constexpr (PEN) {
+      double ps = 0.0;
+      for (int q = 0; q < nblk; ++q) ps += wred[q];
+      Jv = fma(sp.pen_mu, ps, Jv);
+    }
     // J is the one value other workgroups read in this launch (publish): stored write-through at agent scope (sc1),
     // so the hand-off needs no release fence (no L2 write-back of everything this XCD holds dirty)
     __hip_atomic_store(reinterpret_cast<unsigned long long*>(g.J + b),
-                       (unsigned long long)__double_as_longlong(red[16]), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (sp.J2) sp.J2[b] = red[16];
+                       (unsigned long long)__double_as_longlong(Jv), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (sp.J2) sp.J2[b] = Jv;
   }
   // J is published after the cost: before the barrier that precedes G_0 when no waves share a SIMD within the
   // workgroup (early: all waves wait for the fences together), else after the last barrier before phase 3, so that
@@ -1067,6 +1304,21 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
 #pragma unroll
     for (int e = 0; e < E; ++e) g0s[e * nblk + beta] = make_double2(cr[e], ci[e]);
   }
+  if constexpr (PEN) {
+    // X_s = Σ_{s' > s} T_s' into H: the next segment's suffix sum within the wave plus the later waves' totals, in a
+    // fixed order (read here, after the last segment's work above, so that X is not live across it; the rows are
+    // overwritten only behind the barrier below)
+    if (pm) {
+      later_waves(Hr, Hi);
+      if (uw0 + 1 < UPW && s + 1 < S)
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          const double2 x = slot_at(s + 1, e);
+          Hr[e] += x.x;
+          Hi[e] += x.y;
+        }
+    }
+  }
   __syncthreads();
   // G at the segment's end: Q_s G_0 Q_s^H
   {
@@ -1076,6 +1328,50 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
       const double2 v = g0s[e * nblk + beta];
       hr[e] = v.x;
       hi[e] = v.y;
+    }
+    if constexpr (PEN) {
+      // (entry by entry, each stored or added at once, and the three parts kept apart: few matrices live at a time)
+      if (pm) {
+        double dr[E], di[E];
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          const double2 v = d0s[e * nblk + beta];
+          dr[e] = v.x;
+          di[e] = v.y;
+        }
+        // D at the segment's end, Q_s D_0 Q_s^H: phase 3's start, in the lane's LDS row (fused) or to HBM (forward)
+        seg_mm<NB, false, false>(qr, qi, dr, di, tr, ti);
+#pragma unroll
+        for (int i = 0; i < NB; ++i)
+#pragma unroll
+          for (int j = 0; j < NB; ++j) {
+            double sr = 0.0, si = 0.0;
+#pragma unroll
+            for (int q = 0; q < NB; ++q) {
+              sr = fma(tr[i * NB + q], qr[j * NB + q], fma(ti[i * NB + q], qi[j * NB + q], sr));
+              si = fma(ti[i * NB + q], qr[j * NB + q], fma(-tr[i * NB + q], qi[j * NB + q], si));
+            }
+            if constexpr (MODE == BLKSEG_FWD) dseg_at(i * NB + j) = make_double2(sr, si);
+            else dl_at(i * NB + j) = make_double2(sr, si);
+          }
+        __builtin_amdgcn_sched_barrier(0);
+        // the later segments' sources in the frame of time 0: G_0 + 2 μ D_0 X_s
+        const double f = 2.0 * sp.pen_mu;
+#pragma unroll
+        for (int i = 0; i < NB; ++i)
+#pragma unroll
+          for (int j = 0; j < NB; ++j) {
+            double sr = 0.0, si = 0.0;
+#pragma unroll
+            for (int q = 0; q < NB; ++q) {
+              sr = fma(dr[i * NB + q], Hr[q * NB + j], fma(-di[i * NB + q], Hi[q * NB + j], sr));
+              si = fma(dr[i * NB + q], Hi[q * NB + j], fma(di[i * NB + q], Hr[q * NB + j], si));
+            }
+            hr[i * NB + j] = fma(f, sr, hr[i * NB + j]);
+            hi[i * NB + j] = fma(f, si, hi[i * NB + j]);
+          }
+        __builtin_amdgcn_sched_barrier(0);
+      }
     }
     seg_mm<NB, false, false>(qr, qi, hr, hi, tr, ti);
     seg_mm<NB, false, true>(tr, ti, qr, qi, Gr, Gi);
@@ -1095,6 +1391,13 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
   BK_T(t3);
   // ---- phase 3: each segment backwards, the gradient of every slice ----
   const double mu1r = sp.mur[1], mu1i = sp.mui[1], mu2r = sp.mur[2], mu2i = sp.mui[2];
+  // PEN, one slice: G_{k+1} takes the source of λ_{k+1}, 2 μ D_{k+1} Π; then D_k = U_k^H D_{k+1} U_k.  D is read from
+  // and written back to the lane's LDS row through an opaque copy of the segment index, so that the compiler does not
+  // promote the row to registers over the loop (where it would be live across the contraction)
+  const double pen2 = PEN ? 2.0 * sp.pen_mu : 0.0;
+  auto pen_step = [&](const double (&ur)[E], const double (&ui)[E]) {
+    seg_pen_step<NB>(pm, pen2, slot + (size_t)opaque(s) * E * nblk + beta, nblk, ur, ui, Gr, Gi);
+  };
   double* const wr = wred + 128 * RB * w;
   // the slices' sums over their blocks: each step's partial sums go to slot (L - 1 - jj) % RB of a wave-private
   // area; every RB steps (and after the last) one lane per (step, segment of the wave, control) adds its nblk
@@ -1140,6 +1443,10 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
       Sk2 ah;
       double ur[4], ui[4];
       sk2_form<KS, ZD>(gk, *reinterpret_cast<const double2*>(r), u, ah, ur, ui, ct0, st0, za0);
+      if constexpr (PEN) {
+        // G_{k+1} takes the source of λ_{k+1}, 2 μ D_{k+1} Π; then D_k = U_k^H D_{k+1} U_k
+        if (pm && (!SEL || act)) pen_step(ur, ui);
+      }
       // K_k = U_k^H G_{k+1}, G_k = K_k U_k
       double Kr[4], Ki[4], tr[4], ti[4];
       seg_mm<2, true, false>(ur, ui, Gr, Gi, Kr, Ki);
@@ -1193,6 +1500,10 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
       const auto gen = gen_at(GREG ? beta : opaque(beta));
       double ar[1][E], ai[1][E], ur[1][E], ui[1][E];
       seg_form<NB, 1>(gen, rk, s0, P, J, ar, ai, ur, ui);
+      if constexpr (PEN) {
+        // G_{k+1} takes the source of λ_{k+1}, 2 μ D_{k+1} Π; then D_k = U_k^H D_{k+1} U_k
+        if (pm && act) pen_step(ur[0], ui[0]);
+      }
       // K_k = U_k^H G_{k+1}, G_k = K_k U_k
       double Kr[E], Ki[E], tr[E], ti[E];
       seg_mm<NB, true, false>(ur[0], ui[0], Gr, Gi, Kr, Ki);

@@ -804,9 +804,14 @@ int qoc_set_state_penalty(qoc_ctx* c, const int* P, int np, const int* C, int nc
       if (col >= 0) mask[P[a] + (size_t)c->N * col] = 1;
     }
   }
+  HIPCHK(c, hipSetDevice(c->dev));
+  if (int r0 = blk_materialize(c)) return r0;  // λ_k kept lazily is rebuilt with the penalty of its own eval
   c->h_pen_rows.assign(P, P + np);
   c->h_pen_cols.assign(C, C + nc);
-  HIPCHK(c, hipSetDevice(c->dev));
+  // what the segmented eval keeps of the penalty: its row / column masks (and with them the shape key), and the G and
+  // D a split forward stored at the segment ends, which carry the old penalty (the backward then rebuilds x_k)
+  c->seg_pen_valid = false;
+  if (c->fwd_kind == 1) c->fwd_kind = 0;
   // kernels queued by the asynchronous entry points may still read the mask: finish them first (the engine
   // stream is non-blocking, a null-stream copy would not wait for it)
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -818,6 +823,7 @@ int qoc_set_state_penalty(qoc_ctx* c, const int* P, int np, const int* C, int nc
 int qoc_set_costate_source(qoc_ctx* c, const double* dLdx) {
   if (!c) return fail(nullptr, QOC_ERR_ARG, "null context");
   HIPCHK(c, hipSetDevice(c->dev));
+  if (int r0 = blk_materialize(c)) return r0;  // λ_k kept lazily belongs to an eval without this source
   HIPCHK(c, hipStreamSynchronize(c->stream));  // queued backward kernels may still read the old source
   if (!dLdx) {
     c->src_on = false;

@@ -200,12 +200,18 @@ struct qoc_ctx {
   double2* d_gseg = nullptr;         // B x NB^2 x S x nblk complex
   size_t gseg_bytes = 0;
   // the segmented eval's launch shape, kept between evals: valid while the sizes it was derived from (seg_key: B, Nt,
-  // N, m, nu, block rows, blocks) are the context's; the QOC_BLKSEG_W / _S / _RB switches are read when it is
-  // derived.  seg_attr[NB - 2][order - 1][mode]: this context has raised that k_blkseg_eval instance's dynamic-LDS
-  // limit (blkseg_lds_attr)
+  // N, m, nu, block rows, blocks, penalised or not) are the context's; the QOC_BLKSEG_W / _S / _RB switches are read
+  // when it is derived.  seg_attr[NB - 2][order - 1][mode][penalised]: this context has raised that k_blkseg_eval
+  // instance's dynamic-LDS limit (blkseg_lds_attr)
   mutable BlksegShape seg_shape{};
-  mutable int seg_key[7] = {-1, -1, -1, -1, -1, -1, -1};
-  bool seg_attr[2][4][3] = {};
+  mutable int seg_key[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+  bool seg_attr[2][4][3][2] = {};  // [..][penalised]
+  // the state penalty as the segmented eval takes it (blkseg_pen): per block row i a bit mask over the blocks
+  // (seg_prow[i], bit β: row i of block β is in P) and a bit mask over the columns C; derived from h_pen_rows /
+  // h_pen_cols and the block rows h_brow, invalidated by qoc_set_state_penalty and by a new block layout
+  mutable bool seg_pen_valid = false;
+  mutable unsigned int seg_prow[3] = {0, 0, 0}, seg_pcol = 0;
+  std::vector<int> h_brow;           // nblk x blk_nb rows of each block (-1 padding), the host's copy of d_brow
   int* h_flag = nullptr;             // host-mapped stale-u flag of the queued check (k_compare_u_flags)
   int flag_turn = 0;                 // which of the two device flags d_flag[0 / 1] the next queued check writes
   hipEvent_t flag_ev = nullptr;      // recorded after that copy

@@ -25,6 +25,8 @@ int blk_detect(qoc_ctx* c) {
   c->blk_jr = 0;
   c->blk_real = false;
   c->nwb = 0;
+  c->h_brow.clear();
+  c->seg_pen_valid = false;  // the penalty's row masks follow the block layout (blkseg_pen)
   const char* env = getenv("QOC_BLOCKS");
   if (env && !std::strcmp(env, "0")) return QOC_OK;
   const bool valu = env && !std::strcmp(env, "valu");  // blocks of <= 4 rows on the VALU lanes (k_blk_*)
@@ -113,6 +115,7 @@ int blk_detect(qoc_ctx* c) {
     wrow = slot;
   }
   c->h_wrow = wrow;
+  c->h_brow = brow;
   c->h_wrow_live.clear();
   c->h_dead_rows.clear();
   c->dead_dirty = true;
@@ -1590,16 +1593,26 @@ static int blku_bwdg(qoc_ctx* c, int order, double* d_dJdu, const double2* Uin =
 }
 
 // qoc_get_costates after a fused backward: the plain backward chain from the saved u and coefficients into d_L
+// After a penalised segmented eval λ_k carries the source 2 μ x_k[P, C], so the states of the saved u are rebuilt
+// first (into d_X, which then counts as lazy again: the last propagate's u may be another).  qoc_set_state_penalty
+// materialises before it changes the penalty, so the one in force here is the eval's.
+static int blku_states_of(qoc_ctx* c, const double* d_u);
 int blku_costates(qoc_ctx* c) {
   if (!c->L_lazy) return QOC_OK;
   TChainArgs g = tchain_args(c);
   g.coef = c->d_coef_lam;
   g.u = c->d_u_lam;
+  g.src = nullptr;  // (a lazily kept λ never had one: the paths that leave it decline a co-state source)
+  int r = QOC_OK;
+  if (g.pmask) {
+    if ((r = blku_states_of(c, c->d_u_lam))) return r;
+    c->X_lazy = true;
+  }
   const BlkuShape s = blku_shape(c, false);
   BlkuParams bp = blku_params(c, s);
-  int r = blku_records(c, bp, false, c->d_u_lam);
+  r = blku_records(c, bp, false, c->d_u_lam);
   if (r) return r;
-  const hipError_t e = blku_launch_bwd(c, g, s, bp, false);
+  const hipError_t e = blku_launch_bwd(c, g, s, bp, g.pmask != nullptr);
   if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "k_blku_bwd launch: %s", hipGetErrorString(e));
   c->L_lazy = false;
   return QOC_OK;
@@ -1684,9 +1697,30 @@ static int blku_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu) {
 // stale shape.  The cache is the context's (mutable members: blkseg_ok, a predicate on a const context, fills it
 // too); like the rest of a context it is for one host thread at a time.  The reference returned stays valid until
 // the next call with other sizes.
+// The state penalty in the form the segmented eval takes (BlksegParams::prow / pcol): whether the eval is a penalised
+// one (μ != 0 with at least one row and one column; otherwise the unpenalised kernel computes the same J and dJdu).
+// The masks are the context's, derived on first use after qoc_set_state_penalty or a new block layout dropped them.
+static bool blkseg_pen(const qoc_ctx* c) {
+  if (c->mu == 0.0) return false;
+  if (!c->seg_pen_valid) {
+    c->seg_prow[0] = c->seg_prow[1] = c->seg_prow[2] = 0;
+    c->seg_pcol = 0;
+    const int NB = c->blk_nb;
+    if (NB >= 2 && NB <= 3 && c->nblk <= 32 && (int)c->h_brow.size() == c->nblk * NB)
+      for (int r : c->h_pen_rows)
+        for (int q = 0; q < c->nblk * NB; ++q)
+          if (c->h_brow[q] == r) c->seg_prow[q % NB] |= 1u << (q / NB);
+    for (int col : c->h_pen_cols)
+      if (col >= 0 && col < 32) c->seg_pcol |= 1u << col;
+    c->seg_pen_valid = true;
+  }
+  return (c->seg_prow[0] | c->seg_prow[1] | c->seg_prow[2]) != 0 && c->seg_pcol != 0;
+}
+
 static const BlksegShape& blkseg_shape(const qoc_ctx* c) {
-  const int key[7] = {c->B, c->Nt, c->N, c->m, c->nu, c->blk_nb, c->nblk};
-  if (std::equal(key, key + 7, c->seg_key)) return c->seg_shape;
+  const bool pen = blkseg_pen(c);
+  const int key[8] = {c->B, c->Nt, c->N, c->m, c->nu, c->blk_nb, c->nblk, pen ? 1 : 0};
+  if (std::equal(key, key + 8, c->seg_key)) return c->seg_shape;
   BlksegShape& s = c->seg_shape;
   s = BlksegShape{};
   const int per_cu = std::max(1, std::min(8, (c->B + c->ncu - 1) / std::max(1, c->ncu)));
@@ -1704,23 +1738,28 @@ static const BlksegShape& blkseg_shape(const qoc_ctx* c) {
   const int rbmax = std::max(1, 64 / (s.UPW * std::max(1, c->nu)));
   if (c->blk_nb == 2) {
     const int rb8 = std::min(8, rbmax);
-    if (blkseg_lds(c->N, c->m, c->nu, c->blk_nb, c->nblk, c->Nt, s.S, s.W, rb8) <= BLKSEG_LDS_MAX) s.RB = rb8;
+    if (blkseg_lds(c->N, c->m, c->nu, c->blk_nb, c->nblk, c->Nt, s.S, s.W, rb8, pen) <= BLKSEG_LDS_MAX) s.RB = rb8;
   }
   if (const char* e = getenv("QOC_BLKSEG_RB")) s.RB = std::max(1, std::min(atoi(e), rbmax));
-  s.lds = blkseg_lds(c->N, c->m, c->nu, c->blk_nb, c->nblk, c->Nt, s.S, s.W, s.RB);
-  std::copy(key, key + 7, c->seg_key);
+  s.lds = blkseg_lds(c->N, c->m, c->nu, c->blk_nb, c->nblk, c->Nt, s.S, s.W, s.RB, pen);
+  std::copy(key, key + 8, c->seg_key);
   return s;
 }
 
 // The segmented eval applies to block propagators of blocks of <= 3 rows with exactly skew-Hermitian generators
-// (unitary slices), the built-in costs, no penalty and no co-state source; QOC_BLKSEG=0 keeps the forward + fused
-// backward of k_blku_*.
+// (unitary slices), the built-in costs with or without the state penalty (the kernel's PEN instantiations;
+// QOC_BLKSEG_PEN=0 leaves a penalised eval to the k_blku_* chains) and no co-state source (an arbitrary dL/dx needs
+// x_k); QOC_BLKSEG=0 keeps the forward + fused backward of k_blku_*.
 bool blkseg_ok(const qoc_ctx* c, int order) {
   if (!blku_on(c) || (c->blk_nb != 2 && c->blk_nb != 3) || !c->skew_exact || c->nblk > 32) return false;
-  if (order < 1 || order > BLK_ORDMAX || c->mu != 0.0 || c->src_on) return false;
+  if (order < 1 || order > BLK_ORDMAX || c->src_on) return false;
   if (c->cost_kind != QOC_COST_TRACE && c->cost_kind != QOC_COST_ZCAL) return false;
   const char* env = getenv("QOC_BLKSEG");
   if (env && !std::strcmp(env, "0")) return false;
+  if (c->mu != 0.0) {
+    const char* pe = getenv("QOC_BLKSEG_PEN");
+    if ((pe && !std::strcmp(pe, "0")) || c->m > 32) return false;  // (the column mask has 32 bits)
+  }
   return blkseg_shape(c).lds <= BLKSEG_LDS_MAX;
 }
 
@@ -1758,6 +1797,11 @@ static int blkseg_params(qoc_ctx* c, const BlksegShape& s, BlksegParams& sp) {
   sp.RB = s.RB;
   sp.gtab = c->d_gtab;
   sp.terms = c->d_terms;
+  if (blkseg_pen(c)) {  // (else zeros: the unpenalised kernel reads none of them)
+    sp.pen_mu = c->mu;
+    for (int i = 0; i < 3; ++i) sp.prow[i] = c->seg_prow[i];
+    sp.pcol = c->seg_pcol;
+  }
   // the best (J, seed) for qoc_allgather_best_dev, found by the launch's last workgroup
   if (!c->d_best) {  // no communicator yet: this context alone (the epilogue's own layout)
     HIPCHK(c, hipMalloc((void**)&c->d_best, 6 * sizeof(double)));
@@ -1783,8 +1827,8 @@ static int blkseg_params(qoc_ctx* c, const BlksegShape& s, BlksegParams& sp) {
 // once (seg_attr), to the most the eval ever asks for (BLKSEG_LDS_MAX less the kernel's static LDS) and not to its own
 // size, because the limit belongs to the kernel, not to the context: another context with a smaller shape must not
 // lower it
-static hipError_t blkseg_lds_attr(qoc_ctx* c, int nb, int ord, int mode, const void* kern, size_t lds) {
-  bool& set = c->seg_attr[nb - 2][ord - 1][mode];
+static hipError_t blkseg_lds_attr(qoc_ctx* c, int nb, int ord, int mode, bool pen, const void* kern, size_t lds) {
+  bool& set = c->seg_attr[nb - 2][ord - 1][mode][pen ? 1 : 0];
   if (lds <= 65536 || set) return hipSuccess;
   hipFuncAttributes fa{};
   hipError_t e = hipFuncGetAttributes(&fa, kern);
@@ -1804,16 +1848,39 @@ static hipError_t blkseg_launch(qoc_ctx* c, int order, const BlksegShape& s, con
     if constexpr (MODE == BLKSEG_FWD && ORD != 1) {
       return hipErrorInvalidValue;
     } else {
-      auto kern = k_blkseg_eval<NB, ORD, 8, MODE>;
-      const hipError_t q = blkseg_lds_attr(c, NB, ORD, MODE, (const void*)kern, s.lds);
-      if (q != hipSuccess) return q;
-      hipLaunchKernelGGL(kern, dim3(c->B), dim3(64 * s.W), s.lds, c->stream, g, bk, sp);
-      return hipGetLastError();
+      auto launch = [&](auto PEN_) {
+        constexpr bool PEN = decltype(PEN_)::value;
+        // blocks of 3 rows: the penalised eval runs as the forward and the backward half (blkseg_eval), so the fused
+        // penalised kernel, which does not fit its registers there, is never built
+        if constexpr (PEN && NB == 3 && MODE == BLKSEG_FUSED) {
+          return hipErrorInvalidValue;
+        } else {
+          auto kern = k_blkseg_eval<NB, ORD, 8, MODE, PEN>;
+          const hipError_t q = blkseg_lds_attr(c, NB, ORD, MODE, PEN, (const void*)kern, s.lds);
+          if (q != hipSuccess) return q;
+          hipLaunchKernelGGL(kern, dim3(c->B), dim3(64 * s.W), s.lds, c->stream, g, bk, sp);
+          return hipGetLastError();
+        }
+      };
+      // the penalised instantiation when the launch carries a penalty (blkseg_params)
+      if (sp.pen_mu != 0.0) return launch(std::true_type());
+      return launch(std::false_type());
     }
   });
 }
 
 int blkseg_eval(qoc_ctx* c, int order, const double* d_u, double* d_J, double* d_dJdu) {
+  if (blkseg_pen(c) && c->blk_nb == 3) {
+    // Blocks of 3 rows with the penalty: the two halves as two launches (G and D at the segment ends through HBM).
+    // In one kernel the penalised phases 1-2 and phase 3 together spill (416 bytes per lane at order 3), and the two
+    // launches measured faster than that kernel (zz, B = 512: 4.4M against 4.0M evals/s); J and dJdu are bitwise the
+    // same, and each half is within its registers.  The eval leaves no split forward behind.
+    int r = blkseg_forward(c, d_u, d_J);
+    if (r) return r;
+    c->fwd_kind = 0;
+    c->props_since_reset--;  // (counted by the caller)
+    return blkseg_backward(c, order, d_dJdu, nullptr);
+  }
   const BlksegShape s = blkseg_shape(c);
   int r = ensure_lazy_bufs(c);
   if (r) return r;
@@ -1851,8 +1918,10 @@ int blkseg_forward(qoc_ctx* c, const double* d_u, double* d_J) {
   const BlksegShape s = blkseg_shape(c);
   int r = ensure_lazy_bufs(c);
   if (r) return r;
-  const size_t gbytes = (size_t)c->B * s.S * c->nblk * c->blk_nb * c->blk_nb * sizeof(double2);
-  if (c->gseg_bytes < gbytes) {  // a new block layout (qoc_set_generators) may need more
+  // G at every segment's end, and behind it D when the eval is penalised
+  const size_t gcount = (size_t)c->B * s.S * c->nblk * c->blk_nb * c->blk_nb;
+  const size_t gbytes = (blkseg_pen(c) ? 2 : 1) * gcount * sizeof(double2);
+  if (c->gseg_bytes < gbytes) {  // a new block layout (qoc_set_generators) or a penalty may need more
     if (c->d_gseg) {
       HIPCHK(c, hipStreamSynchronize(c->stream));
       HIPCHK(c, hipFree(c->d_gseg));
@@ -1870,6 +1939,7 @@ int blkseg_forward(qoc_ctx* c, const double* d_u, double* d_J) {
   sp.u_copy = d_u != c->d_u ? c->d_u : nullptr;  // the backward half and the stale check read d_u
   sp.J2 = d_J && d_J != c->d_J ? d_J : nullptr;
   sp.gseg = c->d_gseg;  // (the co-states' rebuild source stays the last grape_sensitivity's: the backward writes it)
+  sp.dseg = c->d_gseg + gcount;
   const int mk = mark_begin(c, 1);
   const hipError_t e = blkseg_launch<BLKSEG_FWD>(c, 1, s, sp);
   mark_end(c, mk);
@@ -1895,6 +1965,7 @@ int blkseg_backward(qoc_ctx* c, int order, double* d_dJdu, const int* stale) {
   sp.coef2 = c->d_coef_lam;
   sp.dJdu = d_dJdu;
   sp.gseg = c->d_gseg;
+  sp.dseg = c->d_gseg + (size_t)c->B * s.S * c->nblk * c->blk_nb * c->blk_nb;
   sp.stale = stale;
   const int mk = mark_begin(c, 2);
   const hipError_t e = blkseg_launch<BLKSEG_BWD>(c, order, s, sp);
@@ -1910,6 +1981,12 @@ int blkseg_backward(qoc_ctx* c, int order, double* d_dJdu, const int* stale) {
 // scratch (the eval's own values stay as they were)
 int blku_states(qoc_ctx* c) {
   if (!c->X_lazy) return QOC_OK;
+  const int r = blku_states_of(c, c->d_u);
+  if (r == QOC_OK) c->X_lazy = false;
+  return r;
+}
+// the block forward chain on d_u into d_X
+static int blku_states_of(qoc_ctx* c, const double* d_u) {
   if (!c->d_J_scr) {
     HIPCHK(c, hipMalloc((void**)&c->d_J_scr, (size_t)c->B * sizeof(double)));
     HIPCHK(c, hipMalloc((void**)&c->d_coef_scr, (size_t)c->B * 2 * c->m_user * sizeof(cx<double>)));
@@ -1919,13 +1996,13 @@ int blku_states(qoc_ctx* c) {
   g.J = c->d_J_scr;
   g.coef = c->d_coef_scr;
   g.pmask = nullptr;
+  g.u = d_u;
   const BlkuShape s = blku_shape(c, false);
   BlkuParams bp = blku_params(c, s);
-  int r = blku_records(c, bp, false);
+  int r = blku_records(c, bp, false, d_u);
   if (r) return r;
   const hipError_t e = blku_launch_fwd_g(c, g, s, bp);
   if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "k_blku_fwd launch (states): %s", hipGetErrorString(e));
-  c->X_lazy = false;
   return QOC_OK;
 }
 
