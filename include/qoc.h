@@ -255,6 +255,64 @@ int qoc_allgather_best_dev(qoc_ctx* ctx, double* d_out);
  * after every eval.  The caller keeps the buffer valid while it is registered. */
 int qoc_set_best_output(qoc_ctx* ctx, double* d_out);
 
+/* Device-resident multi-start optimiser (the Ipopt multi-start of examples/zz_coupling_ipopt_exp.jl:56-80 as B
+ * independent projected L-BFGS runs with an augmented-Lagrangian outer loop).  Every seed is a state
+ * machine of its own: at each tick all B trial points are evaluated in one batch and every seed consumes its own
+ * (f, grad): it accepts the trial and posts a new one, halves its step, or ends an augmented-Lagrangian round.  No
+ * host decision lies between two evals.  All optimiser state is fp64.
+ *   n: variables per seed (<= 256); memory: L-BFGS pairs (<= 16); beyond that QOC_ERR_UNSUPPORTED.
+ *   ns, nu: 0 = no constraints; otherwise n == ns * nu and the constraints are the two spline norms
+ *     g = [norm(c), norm(diff(c, dims=1))] <= g_upper (examples/ipopt_callbacks_exp.jl:33-51).
+ *   lower / upper: scalar bounds (+-inf allowed); max_iter: inner iterations per round; outer_iters: augmented-
+ *     Lagrangian rounds; max_ls: trials per line search; rho0: first penalty; gtol: projected-gradient bar;
+ *   order: dUkdp order of the spline form (qoc_minimize_spline_dev). */
+typedef struct qoc_opt qoc_opt;
+typedef struct qoc_opt_params {
+  int n, ns, nu;
+  double lower, upper;
+  double g_upper[2];
+  int max_iter, memory, outer_iters, max_ls;
+  double rho0, gtol;
+  int order;
+} qoc_opt_params;
+/* The object is independent of any engine context: ask (qoc_opt_trial_dev) / tell with any objective.  stream: the
+ * hipStream_t the kernels are queued on (NULL: the default stream); nothing synchronises. */
+int qoc_opt_create(qoc_opt** out, int device, int B, const qoc_opt_params* params);
+void qoc_opt_destroy(qoc_opt* opt);
+/* Starts at clamp(c0) (B x n, device); the first trial is that point. */
+int qoc_opt_start_dev(qoc_opt* opt, void* stream, const double* d_c0);
+/* Device pointer of the B x n trial points (fixed for the object's life). */
+double* qoc_opt_trial_dev(qoc_opt* opt);
+/* f (B) and grad (B x n) at the current trials, device pointers: every seed advances by one tick and the next
+ * trials are written.  A finished seed keeps its iterate as its trial; its state no longer changes. */
+int qoc_opt_tell_dev(qoc_opt* opt, void* stream, const double* d_f, const double* d_grad);
+/* The whole multi-start run on the engine's stream: ticks of (eval, one fused step kernel: dJdc = Bs' dJdu', the
+ * seed's state machine, u = transpose(Bs c) of its next trial written into the context's controls) are queued in
+ * groups of poll_every (<= 0: 16); after each group the host waits on one event and reads the mirrored count of
+ * finished seeds.  Stops when all seeds are done or after max_ticks ticks, QOC_OK either way (qoc_opt_result tells
+ * which).  Then one closing eval at the final iterates: the context's u, J, lazy states and best-(J, seed) epilogue
+ * (qoc_allgather_best) belong to the result.  d_c (B x ns x nu, device): the starts in, the final iterates out.
+ * ticks_out: the ticks the slowest seed used.  QOC_ERR_STATE without a spline basis, QOC_ERR_ARG when B or n differ. */
+int qoc_minimize_spline_dev(qoc_ctx* ctx, qoc_opt* opt, double* d_c, long long max_ticks, int poll_every,
+                            long long* ticks_out);
+/* Device pointers of the per-seed results (valid for the object's life; read them after the stream has drained). */
+#define QOC_OPT_X 0          /* B x n doubles: iterates */
+#define QOC_OPT_F 1          /* B doubles: objective at the iterate (without constraint terms) */
+#define QOC_OPT_G 2          /* B x 2 doubles: constraint values */
+#define QOC_OPT_LAM 3        /* B x 2 doubles: multipliers */
+#define QOC_OPT_RHO 4        /* B doubles: penalty */
+#define QOC_OPT_EVALS 5      /* B ints: evals consumed */
+#define QOC_OPT_ITERS 6      /* B ints: accepted iterations */
+#define QOC_OPT_ROUNDS 7     /* B ints: augmented-Lagrangian rounds ended */
+#define QOC_OPT_CONVERGED 8  /* B ints */
+#define QOC_OPT_DONE 9       /* B ints */
+#define QOC_OPT_LSFAILS 10   /* B ints: failed line searches */
+void* qoc_opt_field_dev(qoc_opt* opt, int field);
+/* Host copies (any pointer may be NULL), after synchronising stream: x (B x n), f (B), g and lam (B x 2), rho (B),
+ * evals / iters / rounds / converged / done / lsfails (B ints each), not_done: seeds that have not finished. */
+int qoc_opt_result(qoc_opt* opt, void* stream, double* x, double* f, double* g, double* lam, double* rho, int* evals,
+                   int* iters, int* rounds, int* converged, int* done, int* lsfails, int* not_done);
+
 /* Standalone ops on the same kernels. */
 /* exponential!(A, ExpMethodHigham2005()) for `count` independent N x N matrices
  * (src/gradient_computations.jl:24, third-party ExponentialUtilities). */

@@ -10,6 +10,7 @@
 
 #include "qoc_internal.hpp"
 #include "qoc_spline.hpp"
+#include "qoc_opt.hpp"
 
 namespace qoc_host {
 
@@ -1669,6 +1670,198 @@ int qoc_expm_jacobian(int device, int N, int nu, const double* A0, const double*
   for (int j = 0; j < nu && !r; ++j) hipMemcpy(dFdp_out + 2 * NN * j, bufs[nu + 5 + j], bytes, hipMemcpyDeviceToHost);
   for (auto b : bufs) hipFree(b);
   return r;
+}
+
+// ---- device-resident multi-start optimiser (qoc_opt.hpp) ----
+
+int qoc_opt_create(qoc_opt** out, int device, int B, const qoc_opt_params* p) {
+  if (!out || !p) return fail(nullptr, QOC_ERR_ARG, "null argument");
+  *out = nullptr;
+  if (B < 1 || p->n < 1 || p->memory < 1 || p->max_ls < 1 || p->max_iter < 0)
+    return fail(nullptr, QOC_ERR_ARG, "invalid optimiser dimensions (B=%d n=%d memory=%d max_ls=%d max_iter=%d)", B, p->n,
+                p->memory, p->max_ls, p->max_iter);
+  if (p->n > OPT_MAX_N || p->memory > OPT_MAX_MEM)
+    return fail(nullptr, QOC_ERR_UNSUPPORTED, "the device optimiser takes n <= %d and memory <= %d (got n=%d memory=%d)",
+                OPT_MAX_N, OPT_MAX_MEM, p->n, p->memory);
+  if (p->ns < 0 || p->nu < 0 || ((p->ns > 0 || p->nu > 0) && (long long)p->ns * p->nu != p->n))
+    return fail(nullptr, QOC_ERR_ARG, "constraints need n == ns * nu (n=%d ns=%d nu=%d)", p->n, p->ns, p->nu);
+  if (!(p->lower <= p->upper)) return fail(nullptr, QOC_ERR_ARG, "lower bound above upper bound");
+  if (p->ns > 0 && !(p->rho0 > 0.0)) return fail(nullptr, QOC_ERR_ARG, "rho0 must be positive");
+  HIPCHK(nullptr, hipSetDevice(device));
+  qoc_opt* o = new qoc_opt();
+  o->dev = device;
+  o->B = B;
+  o->order = p->order;
+  o->P = OptParams{p->n, p->ns, p->nu, p->max_iter, p->memory, p->outer_iters, p->max_ls, p->lower, p->upper,
+                   p->g_upper[0], p->g_upper[1], p->rho0, p->gtol};
+  bool ok = true;
+  auto alloc = [&](size_t bytes) -> void* {
+    void* q = nullptr;
+    if (!ok || hipMalloc(&q, bytes) != hipSuccess) {
+      ok = false;
+      return nullptr;
+    }
+    o->allocs.push_back(q);
+    return q;
+  };
+  const size_t Bn = (size_t)B * p->n;
+  OptState& st = o->st;
+  st.x = (double*)alloc(Bn * 8);
+  st.gx = (double*)alloc(Bn * 8);
+  st.d = (double*)alloc(Bn * 8);
+  st.xt = (double*)alloc(Bn * 8);
+  st.S = (double*)alloc(Bn * p->memory * 8);
+  st.Y = (double*)alloc(Bn * p->memory * 8);
+  st.rec = (double*)alloc((size_t)B * OD_STRIDE * 8);
+  st.f = (double*)alloc((size_t)B * 8);
+  st.g = (double*)alloc((size_t)B * 16);
+  st.lam = (double*)alloc((size_t)B * 16);
+  st.rho = (double*)alloc((size_t)B * 8);
+  st.irec = (int*)alloc((size_t)B * OI_STRIDE * 4);
+  int* cnt = (int*)alloc((size_t)(6 * B + 1) * 4);
+  if (ok && hipHostMalloc((void**)&o->h_done, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent) != hipSuccess)
+    ok = false;
+  if (ok && hipHostGetDevicePointer((void**)&st.host_done, o->h_done, 0) != hipSuccess) ok = false;
+  if (ok && hipEventCreateWithFlags(&o->ev, hipEventDisableTiming) != hipSuccess) ok = false;
+  if (!ok) {
+    qoc_opt_destroy(o);
+    return fail(nullptr, QOC_ERR_HIP, "optimiser workspace allocation failed");
+  }
+  st.evals = cnt;
+  st.iters = cnt + B;
+  st.rounds = cnt + 2 * B;
+  st.converged = cnt + 3 * B;
+  st.done = cnt + 4 * B;
+  st.fails = cnt + 5 * B;
+  st.ndone = cnt + 6 * B;
+  *o->h_done = 0;
+  *out = o;
+  return QOC_OK;
+}
+
+void qoc_opt_destroy(qoc_opt* o) {
+  if (!o) return;
+  hipSetDevice(o->dev);
+  hipDeviceSynchronize();  // queued steps may still use the workspace
+  for (void* q : o->allocs) hipFree(q);
+  if (o->h_done) hipHostFree(o->h_done);
+  if (o->ev) hipEventDestroy(o->ev);
+  delete o;
+}
+
+int qoc_opt_start_dev(qoc_opt* o, void* stream, const double* d_c0) {
+  if (!o || !d_c0) return fail(nullptr, QOC_ERR_ARG, "null argument");
+  HIPCHK(nullptr, hipSetDevice(o->dev));
+  const long long total = (long long)o->B * o->P.n;
+  hipLaunchKernelGGL(k_opt_start, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, o->B, o->P,
+                     o->st, d_c0);
+  HIPCHK(nullptr, hipGetLastError());
+  return QOC_OK;
+}
+
+double* qoc_opt_trial_dev(qoc_opt* o) { return o ? o->st.xt : nullptr; }
+
+int qoc_opt_tell_dev(qoc_opt* o, void* stream, const double* d_f, const double* d_grad) {
+  if (!o || !d_f || !d_grad) return fail(nullptr, QOC_ERR_ARG, "null argument");
+  HIPCHK(nullptr, hipSetDevice(o->dev));
+  hipLaunchKernelGGL(k_opt_tell, dim3((unsigned)((o->B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, o->B, o->P, o->st,
+                     d_f, d_grad);
+  HIPCHK(nullptr, hipGetLastError());
+  return QOC_OK;
+}
+
+void* qoc_opt_field_dev(qoc_opt* o, int field) {
+  if (!o) return nullptr;
+  const OptState& st = o->st;
+  switch (field) {
+    case QOC_OPT_X: return st.x;
+    case QOC_OPT_F: return st.f;
+    case QOC_OPT_G: return st.g;
+    case QOC_OPT_LAM: return st.lam;
+    case QOC_OPT_RHO: return st.rho;
+    case QOC_OPT_EVALS: return st.evals;
+    case QOC_OPT_ITERS: return st.iters;
+    case QOC_OPT_ROUNDS: return st.rounds;
+    case QOC_OPT_CONVERGED: return st.converged;
+    case QOC_OPT_DONE: return st.done;
+    case QOC_OPT_LSFAILS: return st.fails;
+  }
+  return nullptr;
+}
+
+int qoc_opt_result(qoc_opt* o, void* stream, double* x, double* f, double* g, double* lam, double* rho, int* evals,
+                   int* iters, int* rounds, int* converged, int* done, int* lsfails, int* not_done) {
+  if (!o) return fail(nullptr, QOC_ERR_ARG, "null optimiser");
+  HIPCHK(nullptr, hipSetDevice(o->dev));
+  HIPCHK(nullptr, hipStreamSynchronize((hipStream_t)stream));
+  const size_t B = (size_t)o->B;
+  const OptState& st = o->st;
+  if (x) HIPCHK(nullptr, hipMemcpy(x, st.x, B * o->P.n * 8, hipMemcpyDeviceToHost));
+  if (f) HIPCHK(nullptr, hipMemcpy(f, st.f, B * 8, hipMemcpyDeviceToHost));
+  if (g) HIPCHK(nullptr, hipMemcpy(g, st.g, B * 16, hipMemcpyDeviceToHost));
+  if (lam) HIPCHK(nullptr, hipMemcpy(lam, st.lam, B * 16, hipMemcpyDeviceToHost));
+  if (rho) HIPCHK(nullptr, hipMemcpy(rho, st.rho, B * 8, hipMemcpyDeviceToHost));
+  if (evals) HIPCHK(nullptr, hipMemcpy(evals, st.evals, B * 4, hipMemcpyDeviceToHost));
+  if (iters) HIPCHK(nullptr, hipMemcpy(iters, st.iters, B * 4, hipMemcpyDeviceToHost));
+  if (rounds) HIPCHK(nullptr, hipMemcpy(rounds, st.rounds, B * 4, hipMemcpyDeviceToHost));
+  if (converged) HIPCHK(nullptr, hipMemcpy(converged, st.converged, B * 4, hipMemcpyDeviceToHost));
+  if (done) HIPCHK(nullptr, hipMemcpy(done, st.done, B * 4, hipMemcpyDeviceToHost));
+  if (lsfails) HIPCHK(nullptr, hipMemcpy(lsfails, st.fails, B * 4, hipMemcpyDeviceToHost));
+  if (not_done) {
+    int nd = 0;
+    HIPCHK(nullptr, hipMemcpy(&nd, st.ndone, 4, hipMemcpyDeviceToHost));
+    *not_done = o->B - nd;
+  }
+  return QOC_OK;
+}
+
+int qoc_minimize_spline_dev(qoc_ctx* c, qoc_opt* o, double* d_c, long long max_ticks, int poll_every,
+                            long long* ticks_out) {
+  if (!c) return fail(nullptr, QOC_ERR_ARG, "null context");
+  if (!o || !d_c) return fail(c, QOC_ERR_ARG, "null argument");
+  if (!c->ns) return fail(c, QOC_ERR_STATE, "spline basis not set (qoc_set_spline_basis)");
+  if (o->B != c->B || o->dev != c->dev)
+    return fail(c, QOC_ERR_ARG, "the optimiser has B=%d on device %d, the context B=%d on device %d", o->B, o->dev, c->B,
+                c->dev);
+  if (o->P.ns != c->ns || o->P.nu != c->nu || o->P.n != c->ns * c->nu)
+    return fail(c, QOC_ERR_ARG, "the optimiser has n=%d (ns=%d, nu=%d), the context ns=%d, nu=%d", o->P.n, o->P.ns,
+                o->P.nu, c->ns, c->nu);
+  if (max_ticks < 0) return fail(c, QOC_ERR_ARG, "max_ticks must be >= 0");
+  if (c->cost_kind == QOC_COST_EXTERNAL)
+    return fail(c, QOC_ERR_STATE, "qoc_minimize_spline_dev needs a device-side cost (TRACE or ZCAL)");
+  int r = check_ready(c);
+  if (r) return r;
+  if (poll_every <= 0) poll_every = 16;
+  const int order = o->order;
+  if ((r = qoc_opt_start_dev(o, c->stream, d_c))) return fail(c, r, "%s", g_err.c_str());
+  const long long nuT = (long long)c->B * c->Nt * c->nu;
+  const unsigned blocks = (unsigned)std::min<long long>((nuT + 255) / 256, 4096);
+  hipLaunchKernelGGL(k_spline_u, dim3(blocks), dim3(256), 0, c->stream, c->B, c->Nt, c->ns, c->nu, c->d_Bs,
+                     (const double*)o->st.xt, c->d_u);
+  HIPCHK(c, hipGetLastError());
+  long long ticks = 0;
+  while (ticks < max_ticks) {
+    const long long group = std::min<long long>(poll_every, max_ticks - ticks);
+    for (long long t = 0; t < group; ++t) {
+      // the eval on the context's own controls, then the seeds' steps, which write the next trials' controls there
+      if ((r = qoc_eval_dev(c, c->d_u, order, c->d_J, c->d_dJdu))) return r;
+      hipLaunchKernelGGL(k_opt_step_spline, dim3(c->B), dim3(256), 0, c->stream, o->P, o->st, c->Nt,
+                         (const double*)c->d_Bs, (const double*)c->d_dJdu, (const double*)c->d_J, c->d_u);
+      HIPCHK(c, hipGetLastError());
+    }
+    ticks += group;
+    HIPCHK(c, hipEventRecord(o->ev, c->stream));
+    HIPCHK(c, hipEventSynchronize(o->ev));
+    if (*(volatile int*)o->h_done >= o->B) break;
+  }
+  // closing eval at the final iterates: u, J, the lazy states and the best-(J, seed) epilogue are the result's
+  if ((r = qoc_eval_spline_dev(c, o->st.x, order, c->d_J, nullptr))) return r;
+  HIPCHK(c, hipMemcpyAsync(d_c, o->st.x, (size_t)c->B * o->P.n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  std::vector<int> ev(c->B);
+  HIPCHK(c, hipMemcpyAsync(ev.data(), o->st.evals, (size_t)c->B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (ticks_out) *ticks_out = *std::max_element(ev.begin(), ev.end());
+  return QOC_OK;
 }
 
 }  // extern "C"

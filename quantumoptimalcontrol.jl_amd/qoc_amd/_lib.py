@@ -29,6 +29,18 @@ QOC_PROP_TSIT5 = 1
 QOC_ENV = {"tunable_bus": 0, "drag": 1, "sinebasis": 2}
 QOC_CHAIN = {"auto": -1, "propagators": 0, "taylor": 1}
 
+# qoc_opt_field_dev fields
+QOC_OPT_X, QOC_OPT_F, QOC_OPT_G, QOC_OPT_LAM, QOC_OPT_RHO = 0, 1, 2, 3, 4
+QOC_OPT_EVALS, QOC_OPT_ITERS, QOC_OPT_ROUNDS, QOC_OPT_CONVERGED, QOC_OPT_DONE, QOC_OPT_LSFAILS = 5, 6, 7, 8, 9, 10
+
+
+class OptParams(C.Structure):
+    """qoc_opt_params (include/qoc.h)."""
+    _fields_ = [("n", C.c_int), ("ns", C.c_int), ("nu", C.c_int), ("lower", C.c_double), ("upper", C.c_double),
+                ("g_upper", C.c_double * 2), ("max_iter", C.c_int), ("memory", C.c_int), ("outer_iters", C.c_int),
+                ("max_ls", C.c_int), ("rho0", C.c_double), ("gtol", C.c_double), ("order", C.c_int)]
+
+
 # Every symbol include/qoc.h declares, with (restype, argtypes).
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -77,6 +89,14 @@ SIGNATURES = {
     "qoc_propagate_spline": (C.c_int, [_vp, _dp, _dp]),
     "qoc_sensitivity_spline": (C.c_int, [_vp, _dp, C.c_int, _dp]),
     "qoc_spline_constraints_dev": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "qoc_opt_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.POINTER(OptParams)]),
+    "qoc_opt_destroy": (None, [_vp]),
+    "qoc_opt_start_dev": (C.c_int, [_vp, _vp, _vp]),
+    "qoc_opt_trial_dev": (_vp, [_vp]),
+    "qoc_opt_tell_dev": (C.c_int, [_vp, _vp, _vp, _vp]),
+    "qoc_opt_field_dev": (_vp, [_vp, C.c_int]),
+    "qoc_opt_result": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip, _ip, _ip, _ip, _ip]),
+    "qoc_minimize_spline_dev": (C.c_int, [_vp, _vp, _vp, C.c_longlong, C.c_int, C.POINTER(C.c_longlong)]),
     "qoc_gemm_stats": (C.c_int, [_vp, _dp, C.POINTER(C.c_longlong), _dp, C.c_int]),
     "qoc_expm_batched": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip, _ip]),
     "qoc_expm_jacobian": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.POINTER(_dp), _dp, C.c_int, C.c_double, _dp]),

@@ -273,6 +273,16 @@ class GrapeEngine:
         self._chk(self._lib.qoc_spline_constraints_dev(self._h, C.c_void_p(d_c), C.c_void_p(d_g),
                                                        C.c_void_p(d_gjac) if d_gjac else None))
 
+    def minimize_spline_device(self, opt, d_c: int, max_ticks: int, poll_every: int = 16) -> int:
+        """The whole multi-start run on the engine's stream (qoc_minimize_spline_dev): opt is an
+        optimize.DeviceOptimizer with this engine's B and n = ns * nu; d_c (B x nu x ns doubles on the device)
+        holds the starts and receives the final iterates.  Ends with one closing eval at those iterates, so
+        allgather_best() is the best final objective.  Returns the ticks the slowest seed used."""
+        ticks = C.c_longlong()
+        self._chk(self._lib.qoc_minimize_spline_dev(self._h, opt._h, C.c_void_p(d_c), int(max_ticks), int(poll_every),
+                                                    C.byref(ticks)))
+        return int(ticks.value)
+
     def stream(self) -> int:
         return self._lib.qoc_stream(self._h)
 

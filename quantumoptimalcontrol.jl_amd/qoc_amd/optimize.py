@@ -13,6 +13,10 @@ dJdc = Bs' dJdu').  Bounds are handled by projection (projected L-BFGS, Ipopt's
 Lagrangian outer loop.  All vector work is batched torch on the engine's device; the optimiser
 itself is generic over ``fg`` / ``cons`` callables, so the CPU tests drive it with analytic functions.
 
+The lock-step is a scheduling choice: ``minimize_ticks`` runs the same algorithm as one state machine per seed (no
+seed waits for another's line search), and ``minimize_on_device`` / ``DeviceOptimizer`` run those machines on the GPU
+(csrc/qoc_opt.hpp) with no host decision between evals.
+
 Variable layout: c is (B, nc) with nc = ns * nu in Julia's ``c[:]`` order of ``reshape(c, ns, nu)``
 (index s + ns * j), which is also the engine's device layout.
 """
@@ -222,3 +226,356 @@ def minimize_batched(fg, c0, lower=None, upper=None, cons=None, g_upper=None, ma
         prev_viol = viol
     return BatchResult(c=x, f=f_true, g=gval, lam=lam if cons is not None else None, history=history,
                        n_evals=evals, converged=converged)
+
+
+# ---------------------------------------------------------------------------------------------
+# Per-seed state machines: the same algorithm with no seed waiting for another
+# ---------------------------------------------------------------------------------------------
+@dataclass
+class TickResult(BatchResult):
+    """BatchResult of a per-seed run.  n_evals is the tick count (batched evals); history stays empty."""
+    evals: object = None      # (B,) evals each seed consumed before it was done
+    iters: object = None      # (B,) accepted iterations
+    rounds: object = None     # (B,) augmented-Lagrangian rounds ended
+    ls_fails: object = None   # (B,) failed line searches
+    done: object = None       # (B,) bool
+    rho: object = None        # (B,) penalty
+    ticks: int = 0
+    not_done: int = 0
+
+
+_INIT, _LS, _DONE = 0, 1, 2
+
+
+class _Seed:
+    """One seed's state machine (numpy, fp64): the per-seed semantics of ``minimize_batched``, quirks included.
+    ``csrc/qoc_opt.hpp`` opt_tell runs the same rules on the device."""
+
+    def __init__(self, x, lo, hi, ng, p):
+        self.p = p
+        self.lo, self.hi = lo, hi
+        self.x = np.minimum(np.maximum(x, lo), hi)
+        self.xt = self.x.copy()
+        n, m = x.size, p["memory"]
+        self.S, self.Y = np.zeros((m, n)), np.zeros((m, n))
+        self.rinv = np.zeros(m)
+        self.valid = np.zeros(m, dtype=bool)
+        self.head = self.it = self.ls = self.round = 0
+        self.lam = np.zeros(ng)
+        self.rho = p["rho0"]
+        self.prev_viol = 0.0
+        self.phase = _INIT
+        self.converged = False
+        self.evals = self.iters = self.fails = 0
+        self.fx = self.f_true = 0.0
+        self.gx = np.zeros(n)
+        self.gval = np.zeros(ng)
+        self.d = np.zeros(n)
+        self.alpha = 0.0
+
+    def tell(self, f, gr, gv, gj):
+        if self.phase == _DONE:
+            return
+        p = self.p
+        self.evals += 1
+        if gv is None:
+            phi, gphi = f, gr
+        else:
+            t = gv - p["gu"]
+            a = np.maximum(self.lam + self.rho * t, 0.0)
+            phi = f + ((a * a) - self.lam * self.lam).sum() / (2 * self.rho)
+            gphi = gr + (a[:, None] * gj).sum(0)
+        if self.phase == _INIT:
+            self._take(phi, gphi, f, gv)
+            self.valid[:] = False
+            self.head = self.it = 0
+            return self._new_direction()
+        xt, x = self.xt, self.x
+        ok = bool(phi <= self.fx + 1e-4 * (self.gx * (xt - x)).sum()) and bool(np.isfinite(phi))
+        m = p["memory"]
+        if ok:
+            s, y = xt - x, gphi - self.gx
+            sy = (s * y).sum()
+            upd = bool(sy > 1e-12 * np.sqrt((s * s).sum()) * np.sqrt((y * y).sum()))
+            if upd:
+                self.S[self.head], self.Y[self.head], self.rinv[self.head] = s, y, 1.0 / sy
+            self.valid[self.head] = upd
+            self.head = (self.head + 1) % m
+            self.x = xt.copy()
+            self._take(phi, gphi, f, gv)
+            self.it += 1
+            self.iters += 1
+            return self._new_direction()
+        self.ls += 1
+        if self.ls == p["max_ls"]:  # the line search failed: steepest descent from x
+            self.head = (self.head + 1) % m
+            self.valid[:] = False
+            self.it += 1
+            self.fails += 1
+            return self._new_direction()
+        self.alpha *= 0.5
+        self.xt = np.minimum(np.maximum(x + self.alpha * self.d, self.lo), self.hi)
+
+    def _take(self, phi, gphi, f, gv):
+        self.fx, self.gx, self.f_true = float(phi), np.array(gphi, dtype=np.float64), float(f)
+        if gv is not None:
+            self.gval = np.array(gv, dtype=np.float64)
+
+    def _two_loop(self, q):
+        m = self.p["memory"]
+        order = [(self.head - 1 - i) % m for i in range(m)]  # newest first
+        al = np.zeros(m)
+        q = q.copy()
+        for i in order:
+            if self.valid[i]:
+                al[i] = self.rinv[i] * (self.S[i] * q).sum()
+                q = q - al[i] * self.Y[i]
+        nw = order[0]
+        gamma = 1.0
+        if self.valid[nw]:
+            yy = (self.Y[nw] * self.Y[nw]).sum()
+            if yy > 0:
+                gamma = (self.S[nw] * self.Y[nw]).sum() / yy
+        r = gamma * q
+        for i in reversed(order):
+            if self.valid[i]:
+                b = self.rinv[i] * (self.Y[i] * r).sum()
+                r = r + (al[i] - b) * self.S[i]
+        return r
+
+    def _new_direction(self):
+        p = self.p
+        if self.it == p["max_iter"]:
+            return self._end_round()
+        x, gx = self.x, self.gx
+        free = ~(((x <= self.lo) & (gx > 0)) | ((x >= self.hi) & (gx < 0)))
+        q = gx * free
+        pgn = np.abs(q).max()
+        self.converged = bool(pgn <= p["gtol"])
+        if self.converged:
+            return self._end_round()
+        d = -self._two_loop(q) * free
+        if not (d * gx).sum() < 0:
+            d = -q
+            self.valid[:] = False
+        self.alpha = 1.0 if self.valid.any() else min(1.0 / max(pgn, 1e-12), 1.0)
+        self.d = d
+        self.ls = 0
+        self.xt = np.minimum(np.maximum(x + self.alpha * d, self.lo), self.hi)
+        self.phase = _LS
+
+    def _end_round(self):
+        p = self.p
+        self.xt = self.x.copy()
+        if p["gu"] is None:
+            self.round = 1
+            self.phase = _DONE
+            return
+        t = self.gval - p["gu"]
+        viol = np.maximum(t, 0.0).max()
+        self.lam = np.maximum(self.lam + self.rho * t, 0.0)
+        if self.round > 0 and viol > 0.25 * self.prev_viol:
+            self.rho = self.rho * 10.0
+        self.prev_viol = viol
+        self.round += 1
+        self.phase = _DONE if self.round >= max(1, p["outer_iters"]) else _INIT
+
+
+def _default_max_ticks(max_iter, outer_iters, max_ls, constrained):
+    return max(1, outer_iters if constrained else 1) * (1 + max_iter * max_ls)
+
+
+def minimize_ticks(fg, c0, lower=None, upper=None, cons=None, g_upper=None, max_iter: int = 100, memory: int = 10,
+                   outer_iters: int = 4, rho0: float = 10.0, gtol: float = 1e-9, max_ls: int = 12,
+                   max_ticks: int | None = None) -> TickResult:
+    """Host reference of the per-seed state machine, generic over ``fg`` / ``cons`` as
+    ``minimize_batched`` is.  At every tick all B trial points are evaluated in one batched call and every seed
+    consumes its own (f, grad): it accepts the trial and posts a new one, halves its step, or ends an
+    augmented-Lagrangian round.  Seed by seed the iterates are ``minimize_batched``'s; no seed pays for another's
+    line search.  Stops when every seed is done or after ``max_ticks`` ticks (``not_done`` tells which)."""
+    import torch
+    c0 = torch.as_tensor(c0).to(torch.float64)
+    dev = c0.device
+    X0 = c0.detach().cpu().numpy()
+    B, n = X0.shape
+
+    def bound(v, fill):
+        if v is None:
+            return np.full((B, n), fill)
+        v = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v, dtype=np.float64)
+        return np.broadcast_to(v, (B, n)).astype(np.float64)
+    lo, hi = bound(lower, -np.inf), bound(upper, np.inf)
+    gu = None
+    if cons is not None:
+        gu = np.asarray(g_upper, dtype=np.float64)
+        gu = np.broadcast_to(gu, (B, gu.shape[-1]))
+    par = dict(max_iter=max_iter, memory=memory, outer_iters=outer_iters, rho0=rho0, gtol=gtol, max_ls=max_ls)
+    seeds = [_Seed(X0[b], lo[b], hi[b], 0 if gu is None else gu.shape[1], dict(par, gu=None if gu is None else gu[b]))
+             for b in range(B)]
+    if max_ticks is None:
+        max_ticks = _default_max_ticks(max_iter, outer_iters, max_ls, cons is not None)
+    ticks = 0
+    while ticks < max_ticks and any(s.phase != _DONE for s in seeds):
+        xt = torch.from_numpy(np.stack([s.xt for s in seeds])).to(dev)
+        f, gr = fg(xt)
+        f, gr = f.detach().cpu().numpy(), gr.detach().cpu().numpy()
+        gv = gj = None
+        if cons is not None:
+            gv, gj = cons(xt)
+            gv, gj = gv.detach().cpu().numpy(), gj.detach().cpu().numpy()
+        for b, s in enumerate(seeds):
+            s.tell(f[b], gr[b], None if gv is None else gv[b], None if gj is None else gj[b])
+        ticks += 1
+
+    def T(a, dtype=None):
+        return torch.from_numpy(np.asarray(a, dtype=dtype)).to(dev)
+    return TickResult(
+        c=T(np.stack([s.x for s in seeds])), f=T([s.f_true for s in seeds], np.float64),
+        g=T(np.stack([s.gval for s in seeds])) if cons is not None else None,
+        lam=T(np.stack([s.lam for s in seeds])) if cons is not None else None, history=[], n_evals=ticks,
+        converged=T([s.converged for s in seeds], bool), evals=T([s.evals for s in seeds], np.int64),
+        iters=T([s.iters for s in seeds], np.int64), rounds=T([s.round for s in seeds], np.int64),
+        ls_fails=T([s.fails for s in seeds], np.int64), done=T([s.phase == _DONE for s in seeds], bool),
+        rho=T([s.rho for s in seeds], np.float64) if cons is not None else None, ticks=ticks,
+        not_done=sum(s.phase != _DONE for s in seeds))
+
+
+class _DevView:
+    """A device buffer owned by the library, exposed to torch through __cuda_array_interface__."""
+
+    def __init__(self, ptr: int, shape, typestr: str):
+        self.__cuda_array_interface__ = {"shape": tuple(shape), "typestr": typestr, "data": (int(ptr), False),
+                                         "version": 2, "strides": None}
+
+
+class DeviceOptimizer:
+    """The per-seed state machines on the GPU (include/qoc.h qoc_opt_*; csrc/qoc_opt.hpp), as ask / tell:
+
+        opt.start(c0); loop: f, grad at opt.trial -> opt.tell(f, grad); opt.result()
+
+    Everything is queued on ``stream`` (default: torch's current stream on ``device``, so torch objectives need no
+    synchronisation; pass ``engine.stream()`` to drive it with engine evals) and nothing waits for the host.
+    ns, nu > 0 adds the spline-norm constraints g = [norm(c), norm(diff(c, dims=1))] <= g_upper, n = ns * nu."""
+
+    def __init__(self, B: int, n: int, lower=None, upper=None, ns: int = 0, nu: int = 0, g_upper=None,
+                 max_iter: int = 100, memory: int = 10, outer_iters: int = 4, rho0: float = 10.0, gtol: float = 1e-9,
+                 max_ls: int = 12, order: int = 3, device: int = 0, stream: int | None = None):
+        import ctypes as C
+        from . import _lib as L
+        from .engine import _order
+        self._L, self._lib = L, L.load()
+        gu = (0.0, 0.0) if g_upper is None else tuple(float(v) for v in g_upper)
+        if ns and len(gu) != 2:
+            raise ValueError("g_upper must hold the two spline-norm bounds")
+        p = L.OptParams(n=int(n), ns=int(ns), nu=int(nu), lower=-np.inf if lower is None else float(lower),
+                        upper=np.inf if upper is None else float(upper), g_upper=(C.c_double * 2)(*gu),
+                        max_iter=int(max_iter), memory=int(memory), outer_iters=int(outer_iters), max_ls=int(max_ls),
+                        rho0=float(rho0), gtol=float(gtol), order=_order(order))
+        h = C.c_void_p()
+        L.check(self._lib.qoc_opt_create(C.byref(h), int(device), int(B), C.byref(p)))
+        self._h = h
+        self.B, self.n, self.device, self.constrained = int(B), int(n), int(device), bool(ns)
+        self._stream = stream
+        self.max_ticks = _default_max_ticks(max_iter, outer_iters, max_ls, bool(ns))
+        self._trial = None
+
+    def close(self):
+        if getattr(self, "_h", None) is not None and self._h.value:
+            self._lib.qoc_opt_destroy(self._h)
+            self._h = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def _s(self):
+        import ctypes as C
+        if self._stream is not None:
+            return C.c_void_p(self._stream)
+        import torch
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def start(self, c0):
+        """c0: (B, n) float64 torch tensor on the device; the first trial is clamp(c0)."""
+        import ctypes as C
+        c0 = c0.contiguous()
+        if tuple(c0.shape) != (self.B, self.n) or str(c0.dtype) != "torch.float64" or not c0.is_cuda:
+            raise ValueError(f"c0 must be a float64 device tensor of shape {(self.B, self.n)}")
+        self._keep = c0
+        self._L.check(self._lib.qoc_opt_start_dev(self._h, self._s(), C.c_void_p(c0.data_ptr())))
+
+    @property
+    def trial(self):
+        """(B, n) torch view of the trial points (the library's buffer, rewritten by every tell)."""
+        if self._trial is None:
+            import torch
+            ptr = self._lib.qoc_opt_trial_dev(self._h)
+            self._trial = torch.as_tensor(_DevView(ptr, (self.B, self.n), "<f8"), device=torch.device("cuda", self.device))
+        return self._trial
+
+    def trial_ptr(self) -> int:
+        return int(self._lib.qoc_opt_trial_dev(self._h))
+
+    def field_ptr(self, field: int) -> int:
+        """Device pointer of a per-seed result (``_lib.QOC_OPT_*``)."""
+        return int(self._lib.qoc_opt_field_dev(self._h, int(field)))
+
+    def tell(self, f, grad):
+        """f (B,), grad (B, n): float64 device tensors (or raw device pointers) at the current trials."""
+        import ctypes as C
+        if not isinstance(f, int):
+            f, grad = f.contiguous(), grad.contiguous()
+            self._keep_fg = (f, grad)
+            f, grad = f.data_ptr(), grad.data_ptr()
+        self._L.check(self._lib.qoc_opt_tell_dev(self._h, self._s(), C.c_void_p(f), C.c_void_p(grad)))
+
+    def result(self, ticks: int | None = None) -> TickResult:
+        """Waits for the stream and returns the per-seed results as torch tensors on the device."""
+        import ctypes as C
+        import torch
+        B, n = self.B, self.n
+        x, f, g, lam, rho = np.zeros((B, n)), np.zeros(B), np.zeros((B, 2)), np.zeros((B, 2)), np.zeros(B)
+        ints = [np.zeros(B, dtype=np.int32) for _ in range(6)]
+        nd = C.c_int()
+        dp, ip = C.POINTER(C.c_double), C.POINTER(C.c_int)
+        self._L.check(self._lib.qoc_opt_result(self._h, self._s(), *[a.ctypes.data_as(dp) for a in (x, f, g, lam, rho)],
+                                               *[a.ctypes.data_as(ip) for a in ints], C.byref(nd)))
+        evals, iters, rounds, conv, done, fails = ints
+        dev = torch.device("cuda", self.device)
+
+        def T(a, dtype=None):
+            return torch.from_numpy(np.asarray(a, dtype=dtype)).to(dev)
+        t = int(evals.max()) if ticks is None else int(ticks)
+        return TickResult(c=T(x), f=T(f), g=T(g) if self.constrained else None, lam=T(lam) if self.constrained else None,
+                          history=[], n_evals=t, converged=T(conv != 0), evals=T(evals, np.int64),
+                          iters=T(iters, np.int64), rounds=T(rounds, np.int64), ls_fails=T(fails, np.int64),
+                          done=T(done != 0), rho=T(rho) if self.constrained else None, ticks=t, not_done=int(nd.value))
+
+
+def minimize_on_device(engine, Bs, c0, lower=None, upper=None, g_upper=None, max_iter: int = 100, memory: int = 10,
+                       outer_iters: int = 4, rho0: float = 10.0, gtol: float = 1e-9, max_ls: int = 12, order: int = 3,
+                       max_ticks: int | None = None, poll_every: int = 16) -> TickResult:
+    """The multi-start optimisation of ``minimize_batched(SplineGrape(engine, Bs).fg, c0, ...)`` run on the GPU from
+    start to finish (``GrapeEngine.minimize_spline_device``): per tick one eval and one fused step kernel on the
+    engine's stream, the host only queues launches and polls a finished-seed count every ``poll_every`` ticks.
+    ``g_upper = None`` leaves the two spline-norm constraints unbounded (one round).  Ends with a closing eval at the final iterates, so
+    ``engine.allgather_best()`` is (min f, its seed).  ``history`` is empty; ``n_evals`` is the tick count."""
+    import torch
+    engine.set_spline_basis(Bs)
+    ns, nu, B = engine.ns, engine.nu, engine.B
+    dev = torch.device("cuda", engine.device)
+    c = torch.as_tensor(c0).to(device=dev, dtype=torch.float64).reshape(B, ns * nu).clone().contiguous()
+    torch.cuda.current_stream(dev).synchronize()  # c is produced on torch's stream
+    if g_upper is None:
+        g_upper, outer_iters = (np.inf, np.inf), 1
+    opt = DeviceOptimizer(B, ns * nu, lower, upper, ns=ns, nu=nu, g_upper=g_upper, max_iter=max_iter, memory=memory,
+                          outer_iters=outer_iters, rho0=rho0, gtol=gtol, max_ls=max_ls, order=order,
+                          device=engine.device, stream=engine.stream())
+    try:
+        ticks = engine.minimize_spline_device(opt, c.data_ptr(), opt.max_ticks if max_ticks is None else max_ticks,
+                                              poll_every)
+        return opt.result(ticks)
+    finally:
+        opt.close()
