@@ -37,7 +37,9 @@ extern "C" {
 
 /* dUkdp_order: 1..4 = truncated Taylor series of expm_jacobian! (src/gradient_computations.jl:177-213,
  * the reference's definition; 3 in the Ipopt path); QOC_DUKDP_EXACT = exact Fréchet derivative of the
- * propagator (opt-in, SURVEY.md §8f item 2: one 2N x 2N block exponential per slice). */
+ * propagator (opt-in).  Where the segmented eval applies (invariant blocks of <= 3 rows:
+ * cavity, zz) it is that kernel's exact contraction, the whole series of the trace form, closed form on blocks of
+ * 2 rows; elsewhere, or with QOC_BLKSEG_EXACT=0, one 2N x 2N block exponential per slice and control. */
 #define QOC_DUKDP_EXACT 0
 
 #define QOC_COST_TRACE 0     /* J = 1-|tr(X'x)|^2/n^2            (src/penalty_fcns.jl:15-24) */

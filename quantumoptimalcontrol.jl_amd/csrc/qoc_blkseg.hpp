@@ -20,6 +20,12 @@
 //            the trace form of expm_jacobian! + _compute_u_sensitivity (:177-223, blku_contract) on K_k:
 //              dJ/du_jk = Re tr(A_j M_k),  M = Σ_{a+b<ORD} X^b K X^a / (a+b+1)!,  X = A_k,
 //            summed over the slice's blocks (a wave-private LDS slot, fixed order: no atomics).
+//            ORD 0 is the exact (Fréchet) gradient, dUkdp_order = QOC_DUKDP_EXACT: the whole series
+//              M = Σ_{a,b >= 0} X^b K X^a / (a+b+1)! = ∫_0^1 e^{sX} K e^{(1-s)X} ds
+//            on the same K_k and X, so that dJdu is the derivative of the J this kernel computes.  Blocks of 2 rows
+//            without halvings: closed form from the cos ω, sinc ω and e^{μ_k} e^{it} the propagator was formed from
+//            (sk2_contract_exact); otherwise the recurrence as a rolled loop to a term count chosen per seed in
+//            phase 0 (seg_contract_exact, blkseg_exact_terms).  Nothing else of the kernel depends on ORD.
 // Neither x_k, λ_k nor U_k go to HBM: the launch reads u and writes J, the λ_N coefficients and dJdu.  qoc_get_states
 // and qoc_get_costates rebuild x_k / λ_k on demand with the k_blku_* chains (qoc_run_blk.hip).
 //
@@ -192,12 +198,32 @@ constexpr int BLKSEG_KMAX = 9;
 struct BlksegTrig {
   double c[BLKSEG_KMAX + 1];  // (-1)^k / (2k)!
   double s[BLKSEG_KMAX + 1];  // (-1)^k / (2k+1)!
+  double d[BLKSEG_KMAX + 1];  // (-1)^k 2 (k+1) / (2k+3)!: (sin x / x - cos x) / x^2 (the exact contraction's s3)
 };
 // The series degree K (terms up to x^(2K+1)) a seed needs: the first omitted term ρ^(2K+2) / (2K+2)! below 2^-53 for
 // every |x| <= ρ (both ω and |t| are bounded by the seed's largest ρ_k: the eigenvalues i(t ± ω) of a shifted block lie
 // within [-ρ, ρ]).  K = 5 up to ρ = 0.24, 7 up to 0.66, else 9 (covers θ_cap ≈ 0.98); the bounds leave margin
 // (exact limits 0.248 / 0.684 / 1.32).
 __host__ __device__ constexpr int blkseg_series_k(double rho) { return rho <= 0.24 ? 5 : rho <= 0.66 ? 7 : BLKSEG_KMAX; }
+// The exact gradient's generic series (seg_contract_exact): the number of orders n = a + b of
+// M = Σ_{a,b} X^b K X^a / (a+b+1)! to run for a seed whose shifted generators have spectral half-width <= ρ.  Order n
+// has n + 1 words of norm <= ρ^n |K| each, so it is bounded by ρ^n / n! |K| (which covers the rule Σ_{n >= n_ex}
+// ρ^n / (n+1)! <= 2^-53 with room), and the tail behind n_ex by ρ^n_ex / n_ex! / (1 - ρ / (n_ex + 1)).  The smallest
+// n_ex whose bound is <= 2^-53: 9 at ρ = 0.063 (zz, Nt = 500), 11 at 0.17 (cavity, Nt = 1000), 20 at 1.25.  X is
+// skew-Hermitian, so the partial sums grow to e^ρ at most before they fall: the rounding error is e^ρ ε, and the
+// cap of 64 orders (ρ ≈ 16) is far beyond what the fp64 bar allows anyway.
+constexpr int BLKSEG_NEX_MAX = 64;
+__host__ __device__ inline int blkseg_exact_terms(double rho) {
+  const double tol = 1.1102230246251565e-16;
+  double term = 1.0;  // ρ^n / n!
+  int n = 0;
+  while (n < BLKSEG_NEX_MAX) {
+    if (n >= 1 && rho < n + 1 && term <= tol * (1.0 - rho / (n + 1))) break;
+    ++n;
+    term *= rho / n;
+  }
+  return n;
+}
 constexpr BlksegTrig blkseg_trig() {
   BlksegTrig t{};
   double f = 1.0;  // 1 / n!
@@ -206,6 +232,14 @@ constexpr BlksegTrig blkseg_trig() {
     const double sg = (n / 2) % 2 ? -1.0 : 1.0;
     if (n % 2 == 0) t.c[n / 2] = sg * f;
     else t.s[n / 2] = sg * f;
+  }
+  // s3 = (sinc - cos) / x^2 = 1/3 - x^2/30 + x^4/840 - ..: its own series, because the difference cancels at small x.
+  // The term dropped after degree K, 2 (K+2) x^(2K+2) / (2K+5)!, is below the cosine's x^(2K+2) / (2K+2)!, so the
+  // degree classes of blkseg_series_k hold for it as they stand.
+  double f3 = 1.0 / 6.0;  // 1 / (2k+3)!
+  for (int k = 0; k <= BLKSEG_KMAX; ++k) {
+    t.d[k] = (k % 2 ? -1.0 : 1.0) * 2.0 * (k + 1) * f3;
+    f3 /= (double)((2 * k + 4) * (2 * k + 5));
   }
   return t;
 }
@@ -421,9 +455,12 @@ __device__ __forceinline__ void sk2_z(const Sk2& g0, const double* rec, double& 
 // Â = Ã_0 + u_1 Ã_1 + u_2 Ã_2 (no halvings) and U = e^{μ_k} exp(Â) in the closed form of seg_form (ph = e^{μ_k}).
 // ZD: the control generators' blocks have zero diagonals and no shifts, so Â's diagonal is Ã_0's and e^{μ_k} = e^{μ_0}
 // in every slice: z = e^{μ_k} e^{it} comes precomputed (ct0, st0: sk2_z, the same value)
-template <int K = BLKSEG_KMAX, bool ZD = false>
+// EX (the exact contraction, sk2_contract_exact): also hands out ex = [cos ω, sinc ω, s3(ω), Re z, Im z], s3 from a
+// third Horner chain beside the two
+template <int K = BLKSEG_KMAX, bool ZD = false, bool EX = false>
 __device__ __forceinline__ void sk2_form(const Sk2 (&g)[3], double2 ph, double2 u, Sk2& ah, double (&ur)[4],
-                                         double (&ui)[4], double ct0 = 1.0, double st0 = 0.0, double a0 = 0.0) {
+                                         double (&ui)[4], double ct0 = 1.0, double st0 = 0.0, double a0 = 0.0,
+                                         double* ex = nullptr) {
   constexpr BlksegTrig T = blkseg_trig();
   if constexpr (ZD) {  // the same values (u_j times a zero diagonal adds nothing)
     ah.d0 = g[0].d0;
@@ -436,16 +473,24 @@ __device__ __forceinline__ void sk2_form(const Sk2 (&g)[3], double2 ph, double2 
   ah.q = fma(u.y, g[2].q, fma(u.x, g[1].q, g[0].q));
   const double a = ZD ? a0 : 0.5 * (ah.d0 - ah.d1);  // (ZD: a0 the same value, once per lane)
   const double w = fma(a, a, fma(ah.r, ah.r, ah.q * ah.q));
-  double cw = 0.0, sw = 0.0, ct = ct0, st = st0;
+  double cw = 0.0, sw = 0.0, s3 = 0.0, ct = ct0, st = st0;
 #pragma unroll
   for (int k = K; k >= 0; --k) {
     cw = fma(cw, w, T.c[k]);
     sw = fma(sw, w, T.s[k]);
+    if constexpr (EX) s3 = fma(s3, w, T.d[k]);
   }
   if constexpr (!ZD) sk2_phase<K>(ah.d0, ah.d1, ct, st);
   // z = e^{μ_k} e^{it}; ZD (constant shifts too): the same in every slice, (ct0, st0) hold it
   const double zr = ZD ? ct0 : ph.x * ct - ph.y * st, zi = ZD ? st0 : fma(ph.x, st, ph.y * ct);
   const double cr = zr * cw, ci = zi * cw, sr = zr * sw, si = zi * sw;
+  if constexpr (EX) {
+    ex[0] = cw;
+    ex[1] = sw;
+    ex[2] = s3;
+    ex[3] = zr;
+    ex[4] = zi;
+  }
   ur[0] = fma(-si, a, cr);
   ui[0] = fma(sr, a, ci);
   ur[3] = fma(si, a, cr);
@@ -563,6 +608,116 @@ __device__ __forceinline__ void sk2_pauli2(const Sk2& e, double (&a)[4]) {
   a[3] = e.d0 - e.d1;
 }
 
+// The exact (Fréchet) traces in the same basis: the whole series M = Σ_{a,b >= 0} X^b K X^a / (a+b+1)! =
+// ∫_0^1 e^{sX} K e^{(1-s)X} ds.  With z = e^{i x0} (sk2_form's e^{μ_k} e^{it}: x0 = t + Im μ_k), d = x.k and
+// s3 = (sinc ω - cos ω) / ω²,
+//   M = z { [cos ω k0 + i sinc ω d] I + [sinc ω k + (i sinc ω k0 - s3 d) x].σ }
+// (e^{sX} = e^{i s x0} (cos sω + i sin sω x.σ / ω); the products of sines and cosines integrate to sinc, cos and s3;
+// at ω -> 0 it reduces to the order-3 form above).  ex: sk2_form's [cos ω, sinc ω, s3, Re z, Im z].  CX: x3 precomputed.
+template <bool CX = false>
+__device__ __forceinline__ void sk2_contract_exact(const Sk2& x, const double (&a1)[4], const double (&a2)[4],
+                                                   const double (&Kr)[4], const double (&Ki)[4], const double (&ex)[5],
+                                                   double& acc1, double& acc2, double x3c = 0.0) {
+  const double cw = ex[0], sw = ex[1], s3 = ex[2], zr = ex[3], zi = ex[4];
+  const double k0i = Ki[0] + Ki[3], k1i = Ki[1] + Ki[2], k2i = Kr[1] - Kr[2], k3i = Ki[0] - Ki[3];
+  const double k0r = Kr[0] + Kr[3], k1r = Kr[1] + Kr[2], k2r = Ki[2] - Ki[1], k3r = Kr[0] - Kr[3];
+  const double x1 = x.q, x2 = x.r, x3 = CX ? x3c : 0.5 * (x.d0 - x.d1);
+  const double dr = fma(x3, k3r, fma(x2, k2r, x1 * k1r)), di = fma(x3, k3i, fma(x2, k2i, x1 * k1i));
+  // n = M / z (doubled, like K): n0 = cos ω k0 + i sinc ω d, n = sinc ω k + c x with c = i sinc ω k0 - s3 d
+  const double n0r = fma(cw, k0r, -sw * di), n0i = fma(cw, k0i, sw * dr);
+  const double cr = -fma(sw, k0i, s3 * dr), ci = fma(sw, k0r, -s3 * di);
+  // 2 Im m = Re z Im n + Im z Re n
+  const double m0 = fma(zr, n0i, zi * n0r);
+  const double m1 = fma(zr, fma(sw, k1i, ci * x1), zi * fma(sw, k1r, cr * x1));
+  const double m2 = fma(zr, fma(sw, k2i, ci * x2), zi * fma(sw, k2r, cr * x2));
+  const double m3 = fma(zr, fma(sw, k3i, ci * x3), zi * fma(sw, k3r, cr * x3));
+  acc1 = -0.5 * fma(a1[3], m3, fma(a1[2], m2, fma(a1[1], m1, a1[0] * m0)));
+  acc2 = -0.5 * fma(a2[3], m3, fma(a2[2], m2, fma(a2[1], m1, a2[0] * m0)));
+}
+
+// ---- the exact traces on the generic path (blocks of 3 rows; blocks of 2 rows with halvings) ----
+// R <- R X, row by row in place
+template <int NB>
+__device__ __forceinline__ void seg_rx(double (&Rr)[NB * NB], double (&Ri)[NB * NB], const double (&xr_)[NB * NB],
+                                       const double (&xi_)[NB * NB]) {
+#pragma unroll
+  for (int i = 0; i < NB; ++i) {
+    double tr[NB], ti[NB];
+#pragma unroll
+    for (int kk = 0; kk < NB; ++kk) {
+      double sr = 0.0, si = 0.0;
+#pragma unroll
+      for (int q = 0; q < NB; ++q) {
+        sr = fma(Rr[i * NB + q], xr_[q * NB + kk], fma(-Ri[i * NB + q], xi_[q * NB + kk], sr));
+        si = fma(Rr[i * NB + q], xi_[q * NB + kk], fma(Ri[i * NB + q], xr_[q * NB + kk], si));
+      }
+      tr[kk] = sr;
+      ti[kk] = si;
+    }
+#pragma unroll
+    for (int kk = 0; kk < NB; ++kk) {
+      Rr[i * NB + kk] = tr[kk];
+      Ri[i * NB + kk] = ti[kk];
+    }
+  }
+}
+// L <- X L + R, column by column in place
+template <int NB>
+__device__ __forceinline__ void seg_xlr(double (&Lr)[NB * NB], double (&Li)[NB * NB], const double (&Rr)[NB * NB],
+                                        const double (&Ri)[NB * NB], const double (&xr_)[NB * NB],
+                                        const double (&xi_)[NB * NB]) {
+#pragma unroll
+  for (int kk = 0; kk < NB; ++kk) {
+    double tr[NB], ti[NB];
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      double sr = Rr[i * NB + kk], si = Ri[i * NB + kk];
+#pragma unroll
+      for (int q = 0; q < NB; ++q) {
+        sr = fma(xr_[i * NB + q], Lr[q * NB + kk], fma(-xi_[i * NB + q], Li[q * NB + kk], sr));
+        si = fma(xr_[i * NB + q], Li[q * NB + kk], fma(xi_[i * NB + q], Lr[q * NB + kk], si));
+      }
+      tr[i] = sr;
+      ti[i] = si;
+    }
+#pragma unroll
+    for (int i = 0; i < NB; ++i) {
+      Lr[i * NB + kk] = tr[i];
+      Li[i * NB + kk] = ti[i];
+    }
+  }
+}
+// Re tr(A_j M) for j = 1, 2 with the whole series M = Σ_n L_n / (n+1)! (seg_contract's recurrence), nex orders in a
+// rolled loop (nex uniform over the workgroup: blkseg_exact_terms of the seed's largest ρ_k).  The scalar part of
+// X = A_k = Ã_k + μ_k I commutes, M(A_k; K) = e^{μ_k} M(Ã_k; K) = M(Ã_k; e^{μ_k} K): x is the shifted Ã_k, whose
+// spectral half-width the records bound, and K takes the factor (er, ei) = e^{μ_k} first, so that the real traces of
+// seg_trace serve.  The traces are accumulated order by order (three matrices live: K -> L, R, X).  genf(): the generator blocks' accessor, made anew in every pass so that the
+// blocks read from LDS are not hoisted out of the loop.  K is overwritten.
+template <int NB, typename GENF>
+__device__ __forceinline__ void seg_contract_exact(GENF&& genf, const double (&xr_)[NB * NB], const double (&xi_)[NB * NB],
+                                                   double (&Lr)[NB * NB], double (&Li)[NB * NB], int nex, double er,
+                                                   double ei, double m1r, double m1i, double m2r, double m2i,
+                                                   double& acc1, double& acc2) {
+  constexpr int E = NB * NB;
+  double Rr[E], Ri[E];
+#pragma unroll
+  for (int e = 0; e < E; ++e) {
+    const double vr = Lr[e], vi = Li[e];
+    Lr[e] = Rr[e] = er * vr - ei * vi;
+    Li[e] = Ri[e] = fma(er, vi, ei * vr);
+  }
+  acc1 = acc2 = 0.0;
+  seg_trace<NB>(genf(), Lr, Li, 1.0, m1r, m1i, m2r, m2i, acc1, acc2);
+  double f = 1.0;  // 1 / (n+1)!
+#pragma unroll 1
+  for (int n = 1; n < nex; ++n) {
+    seg_rx<NB>(Rr, Ri, xr_, xi_);
+    seg_xlr<NB>(Lr, Li, Rr, Ri, xr_, xi_);
+    f /= (double)(n + 1);
+    seg_trace<NB>(genf(), Lr, Li, f, m1r, m1i, m2r, m2i, acc1, acc2);
+  }
+}
+
 __device__ __forceinline__ double block_max(double v, double* scratch) {
   for (int off = 32; off > 0; off >>= 1) v = fmax(v, __shfl_xor(v, off));
   const int w = threadIdx.x >> 6, l = threadIdx.x & 63;
@@ -669,7 +824,8 @@ __device__ __forceinline__ void seg_pen_step(int pm, double f, double2* dp, int 
 }
 
 // One workgroup per seed (blockIdx.x), W = blockDim / 64 waves, UPW segments of nblk lanes per wave (lanes past
-// UPW nblk idle).  Built-in costs only (TRACE / ZCAL), no co-state source, unpacked states, skew-Hermitian generators
+// UPW nblk idle).  ORD: the gradient's order 1..4, or 0 for the exact one (the header comment's phase 3).
+// Built-in costs only (TRACE / ZCAL), no co-state source, unpacked states, skew-Hermitian generators
 // (the host's blkseg_ok).  PEN: with the state penalty on the rows P and columns C of sp.prow / sp.pcol (the header
 // comment's penalty section); PEN = false is the unpenalised kernel, instruction for instruction.
 template <int NB, int ORD, int WMAX, int MODE = BLKSEG_FUSED, bool PEN = false>
@@ -817,6 +973,9 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
   }
   P = __builtin_amdgcn_readfirstlane(P);
   J = __builtin_amdgcn_readfirstlane(J);
+  // the exact gradient's series length on the generic path (uniform: one seed per workgroup)
+  int nex = 1;
+  if constexpr (ORD == 0) nex = __builtin_amdgcn_readfirstlane(blkseg_exact_terms(rmax));
   if (tid < 8) reinterpret_cast<int*>(red + 24)[tid] = 0;  // wave progress (SegProg)
   if (J) {  // the records hold 2^-J u (exact scaling)
     for (int k = tid; k < Nt; k += nthr) {
@@ -1441,8 +1600,8 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
       const double* r = rec + 4 * (size_t)(act ? k : 0);
       const double2 u = *reinterpret_cast<const double2*>(r + 2);
       Sk2 ah;
-      double ur[4], ui[4];
-      sk2_form<KS, ZD>(gk, *reinterpret_cast<const double2*>(r), u, ah, ur, ui, ct0, st0, za0);
+      double ur[4], ui[4], ex[5];
+      sk2_form<KS, ZD, ORD == 0>(gk, *reinterpret_cast<const double2*>(r), u, ah, ur, ui, ct0, st0, za0, ex);
       if constexpr (PEN) {
         // G_{k+1} takes the source of λ_{k+1}, 2 μ D_{k+1} Π; then D_k = U_k^H D_{k+1} U_k
         if (pm && (!SEL || act)) pen_step(ur, ui);
@@ -1461,7 +1620,9 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
       const double mki = ZD ? sp.mui[0] : fma(u.y, mu2i, fma(u.x, mu1i, sp.mui[0]));
       const Sk2 x{ah.d0 + mki, ah.d1 + mki, ah.r, ah.q};
       double acc1, acc2;
-      if constexpr (ORD <= 3) {
+      if constexpr (ORD == 0) {
+        sk2_contract_exact<ZD>(x, pa1, pa2, Kr, Ki, ex, acc1, acc2, zx3);
+      } else if constexpr (ORD <= 3) {
         sk2_contract_pauli<ORD, ZD>(x, pa1, pa2, Kr, Ki, acc1, acc2, zx0, zx3, zx02);
       } else {
         const Sk2 e1{gk[1].d0 + mu1i, gk[1].d1 + mu1i, gk[1].r, gk[1].q};
@@ -1518,24 +1679,51 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
       const double u1 = ldexp(su.x, J), u2 = ldexp(su.y, J);
       const double mkr = fma(u2, sp.mur[2], fma(u1, sp.mur[1], sp.mur[0]));
       const double mki = fma(u2, sp.mui[2], fma(u1, sp.mui[1], sp.mui[0]));
+      // (the exact series takes the shifted Ã_k and e^{μ_k} as a factor: seg_contract_exact)
+      const double dgr = ORD == 0 ? 0.0 : mkr, dgi = ORD == 0 ? 0.0 : mki;
       double xr[E], xi[E];
       if constexpr (XA) {  // from the formation's Â
 #pragma unroll
         for (int e = 0; e < E; ++e) {
-          xr[e] = (J ? ldexp(ar[0][e], J) : ar[0][e]) + (e % (NB + 1) == 0 ? mkr : 0.0);
-          xi[e] = (J ? ldexp(ai[0][e], J) : ai[0][e]) + (e % (NB + 1) == 0 ? mki : 0.0);
+          xr[e] = (J ? ldexp(ar[0][e], J) : ar[0][e]) + (e % (NB + 1) == 0 ? dgr : 0.0);
+          xi[e] = (J ? ldexp(ai[0][e], J) : ai[0][e]) + (e % (NB + 1) == 0 ? dgi : 0.0);
         }
       } else {  // re-read (blocks of 3 rows: Â is not kept live across the two products)
         const auto gen2 = gen_at(opaque(beta));
 #pragma unroll
         for (int e = 0; e < E; ++e) {
           const double2 g0 = gen2(0, e), g1 = gen2(1, e), g2 = gen2(2, e);
-          xr[e] = fma(u2, g2.x, fma(u1, g1.x, g0.x)) + (e % (NB + 1) == 0 ? mkr : 0.0);
-          xi[e] = fma(u2, g2.y, fma(u1, g1.y, g0.y)) + (e % (NB + 1) == 0 ? mki : 0.0);
+          xr[e] = fma(u2, g2.x, fma(u1, g1.x, g0.x)) + (e % (NB + 1) == 0 ? dgr : 0.0);
+          xi[e] = fma(u2, g2.y, fma(u1, g1.y, g0.y)) + (e % (NB + 1) == 0 ? dgi : 0.0);
         }
       }
       double acc1, acc2;
-      seg_contract<NB, ORD, XA>(gen, xr, xi, Kr, Ki, mu1r, mu1i, mu2r, mu2i, acc1, acc2);
+      // The exact series on blocks of 3 rows keeps X, L and R live over its loop; with G beside them the kernel spills.
+      // G rests in the lane's own row of the segment products' area (free after phase 2; the penalised kernels keep D
+      // there) for the length of the contraction, through opaque copies of the segment index so that the row is not
+      // promoted back to registers.  Lanes without a segment store nothing and read row 0 (their sums are dropped).
+      constexpr bool GST = ORD == 0 && NB == 3 && !PEN;
+      if constexpr (GST) {
+        double2* const gp = slot + (size_t)opaque(sact ? s : 0) * E * nblk + beta;
+        if (sact)
+#pragma unroll
+          for (int e = 0; e < E; ++e) gp[e * nblk] = make_double2(Gr[e], Gi[e]);
+      }
+      if constexpr (ORD == 0) {
+        seg_contract_exact<NB>([&] { return gen_at(GREG ? beta : opaque(beta)); }, xr, xi, Kr, Ki, nex, rk[0][0],
+                               rk[0][1], mu1r, mu1i, mu2r, mu2i, acc1, acc2);
+      } else {
+        seg_contract<NB, ORD, XA>(gen, xr, xi, Kr, Ki, mu1r, mu1i, mu2r, mu2i, acc1, acc2);
+      }
+      if constexpr (GST) {
+        const double2* const gp = slot + (size_t)opaque(sact ? s : 0) * E * nblk + beta;
+#pragma unroll
+        for (int e = 0; e < E; ++e) {
+          const double2 v = gp[e * nblk];
+          Gr[e] = v.x;
+          Gi[e] = v.y;
+        }
+      }
       reduce(jj, act ? acc1 : 0.0, act ? acc2 : 0.0);
     }
   }

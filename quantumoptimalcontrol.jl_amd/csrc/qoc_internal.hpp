@@ -201,11 +201,11 @@ struct qoc_ctx {
   size_t gseg_bytes = 0;
   // the segmented eval's launch shape, kept between evals: valid while the sizes it was derived from (seg_key: B, Nt,
   // N, m, nu, block rows, blocks, penalised or not) are the context's; the QOC_BLKSEG_W / _S / _RB switches are read
-  // when it is derived.  seg_attr[NB - 2][order - 1][mode][penalised]: this context has raised that k_blkseg_eval
+  // when it is derived.  seg_attr[NB - 2][order - 1, exact: 4][mode][penalised]: this context has raised that k_blkseg_eval
   // instance's dynamic-LDS limit (blkseg_lds_attr)
   mutable BlksegShape seg_shape{};
   mutable int seg_key[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
-  bool seg_attr[2][4][3][2] = {};  // [..][penalised]
+  bool seg_attr[2][5][3][2] = {};  // [..][penalised]; order slot 4: the exact instantiation (ORD 0)
   // the state penalty as the segmented eval takes it (blkseg_pen): per block row i a bit mask over the blocks
   // (seg_prow[i], bit β: row i of block β is in P) and a bit mask over the columns C; derived from h_pen_rows /
   // h_pen_cols and the block rows h_brow, invalidated by qoc_set_state_penalty and by a new block layout

@@ -1749,10 +1749,17 @@ static const BlksegShape& blkseg_shape(const qoc_ctx* c) {
 // The segmented eval applies to block propagators of blocks of <= 3 rows with exactly skew-Hermitian generators
 // (unitary slices), the built-in costs with or without the state penalty (the kernel's PEN instantiations;
 // QOC_BLKSEG_PEN=0 leaves a penalised eval to the k_blku_* chains) and no co-state source (an arbitrary dL/dx needs
-// x_k); QOC_BLKSEG=0 keeps the forward + fused backward of k_blku_*.
+// x_k); QOC_BLKSEG=0 keeps the forward + fused backward of k_blku_*.  The exact (Fréchet) gradient is the kernel's
+// ORD 0 instantiation (the whole series of the contraction); QOC_BLKSEG_EXACT=0 leaves an exact eval to the rebuilt
+// x_k / λ_k and the dense Fréchet kernel (dense_gradient), the second implementation the tests compare against.
 bool blkseg_ok(const qoc_ctx* c, int order) {
   if (!blku_on(c) || (c->blk_nb != 2 && c->blk_nb != 3) || !c->skew_exact || c->nblk > 32) return false;
-  if (order < 1 || order > BLK_ORDMAX || c->src_on) return false;
+  const bool exact = order == QOC_DUKDP_EXACT;
+  if ((!exact && (order < 1 || order > BLK_ORDMAX)) || c->src_on) return false;
+  if (exact) {
+    const char* xe = getenv("QOC_BLKSEG_EXACT");
+    if (xe && !std::strcmp(xe, "0")) return false;
+  }
   if (c->cost_kind != QOC_COST_TRACE && c->cost_kind != QOC_COST_ZCAL) return false;
   const char* env = getenv("QOC_BLKSEG");
   if (env && !std::strcmp(env, "0")) return false;
@@ -1763,8 +1770,15 @@ bool blkseg_ok(const qoc_ctx* c, int order) {
   return blkseg_shape(c).lds <= BLKSEG_LDS_MAX;
 }
 
+// (the exact tag has its own dispatch: blk_order_dispatch and BLK_ORDMAX stay the Taylor orders' alone, so the
+// k_blku_*, k_blkp_* and dense kernels keep refusing or routing QOC_DUKDP_EXACT as before)
 template <typename F>
 static hipError_t blkseg_dispatch(int NB, int order, F&& f) {
+  if (order == QOC_DUKDP_EXACT) {
+    const std::integral_constant<int, 0> ex;
+    if (NB == 2) return f(std::integral_constant<int, 2>(), ex);
+    return f(std::integral_constant<int, 3>(), ex);
+  }
   return blk_order_dispatch(order, [&](auto ORD_) {
     if (NB == 2) return f(std::integral_constant<int, 2>(), ORD_);
     return f(std::integral_constant<int, 3>(), ORD_);
@@ -1828,7 +1842,7 @@ static int blkseg_params(qoc_ctx* c, const BlksegShape& s, BlksegParams& sp) {
 // size, because the limit belongs to the kernel, not to the context: another context with a smaller shape must not
 // lower it
 static hipError_t blkseg_lds_attr(qoc_ctx* c, int nb, int ord, int mode, bool pen, const void* kern, size_t lds) {
-  bool& set = c->seg_attr[nb - 2][ord - 1][mode][pen ? 1 : 0];
+  bool& set = c->seg_attr[nb - 2][ord == 0 ? BLK_ORDMAX : ord - 1][mode][pen ? 1 : 0];  // (ORD 0: the exact slot)
   if (lds <= 65536 || set) return hipSuccess;
   hipFuncAttributes fa{};
   hipError_t e = hipFuncGetAttributes(&fa, kern);

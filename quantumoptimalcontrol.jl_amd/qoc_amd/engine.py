@@ -30,7 +30,11 @@ def _ptr(a: np.ndarray):
 
 
 def _order(order) -> int:
-    """dUkdp_order: 1..4 (Taylor, the reference's definition) or "exact" (Fréchet, QOC_DUKDP_EXACT = 0)."""
+    """dUkdp_order: 1..4 (Taylor, the reference's definition) or "exact" (Fréchet, QOC_DUKDP_EXACT = 0).
+
+    "exact" is the derivative of the J the engine computes.  On generators with invariant blocks of <= 3 rows (cavity,
+    zz) it stays on the segmented eval (info()["backward"] == "segmented"), at about the cost of order 3;
+    QOC_BLKSEG_EXACT=0 sends it to the dense Fréchet kernel instead, which every other system uses."""
     if isinstance(order, str):
         if order != "exact":
             raise ValueError(f"dUkdp_order must be 1..4 or 'exact' (got {order!r})")

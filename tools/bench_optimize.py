@@ -9,7 +9,11 @@ Settings of the reference driver (examples/zz_coupling_ipopt_exp.jl:56-80) on zz
 Wall time is taken between device synchronisations.  Reported per leg: wall seconds of every repeat, batched evals or
 ticks, seed-evals/s, iterations/s, best f; and (b)/(c), the cost of a tick over a bare eval, and the share of (b)'s
 seed-ticks spent on seeds that were already done.  Writes profiles/bench_optimize_<tag>.json.
-Usage: python tools/bench_optimize.py [zz|cavity ...] [--tag TAG] [--repeats R] [--B B] [--max-iter K] [--outer R]"""
+--order 3|exact: the gradient every leg runs on (dUkdp_order; "exact" is the derivative of the computed f, and on these
+two systems stays on the segmented eval); the device leg also reports its failed line searches and their share of its
+seed-ticks (each failed search spends max_ls = 12 trials).
+Usage: python tools/bench_optimize.py [zz|cavity ...] [--tag TAG] [--repeats R] [--B B] [--max-iter K] [--outer R]
+       [--order 3|exact]"""
 import json
 import os
 import sys
@@ -38,6 +42,9 @@ REPEATS = opt(args, "--repeats", 3)
 B_OVERRIDE = opt(args, "--B", 0)
 MAX_ITER = opt(args, "--max-iter", 150)
 OUTER = opt(args, "--outer", 2)
+ORDER = opt(args, "--order", "3", str)
+ORDER = "exact" if ORDER == "exact" else int(ORDER)
+MAX_LS = 12  # minimize_on_device's default
 cfgs = args or ["zz", "cavity"]
 
 
@@ -66,7 +73,7 @@ def run(cfg):
     prob, Bs, c0, B, kw = setup(cfg)
     eng = GrapeEngine(prob.A0, prob.A, prob.x0, prob.Nt, B=B)
     eng.set_cost_trace(prob.x_target, prob.n)
-    sg = SplineGrape(eng, Bs)
+    sg = SplineGrape(eng, Bs, order=ORDER)
     c0d = torch.from_numpy(c0).cuda()
     Jd = torch.empty(B, dtype=torch.float64, device="cuda")
     Gd = torch.empty(B, c0.shape[1], dtype=torch.float64, device="cuda")
@@ -78,17 +85,19 @@ def run(cfg):
                     best_f=float(r.f.min()), converged=int(r.converged.sum()))
 
     def device():
-        r = minimize_on_device(eng, Bs, c0d, **kw)
+        r = minimize_on_device(eng, Bs, c0d, order=ORDER, **kw)
         state["ticks"] = r.ticks
         ev = r.evals.cpu().numpy()
         return dict(batched_evals=r.ticks, seed_evals=int(ev.sum()), iterations=int(r.iters.sum()),
                     best_f=float(r.f.min()), converged=int(r.converged.sum()), not_done=r.not_done,
+                    ls_fails=int(r.ls_fails.sum()),
+                    ls_fail_tick_share=float(MAX_LS * int(r.ls_fails.sum()) / max(int(ev.sum()), 1)),
                     evals_min=int(ev.min()), evals_median=float(np.median(ev)), evals_max=int(ev.max()),
                     done_seed_tick_share=float(1.0 - ev.mean() / max(r.ticks, 1)), best=eng.allgather_best())
 
     def bare():
         for _ in range(state["ticks"]):
-            eng.eval_spline_device(c0d.data_ptr(), 3, Jd.data_ptr(), Gd.data_ptr())
+            eng.eval_spline_device(c0d.data_ptr(), ORDER, Jd.data_ptr(), Gd.data_ptr())
         return dict(batched_evals=state["ticks"], seed_evals=B * state["ticks"])
 
     legs = (("lockstep", lockstep), ("device", device), ("bare", bare))
@@ -107,7 +116,9 @@ def run(cfg):
             print(f"{cfg} {name:8s} rep {rep}: {dt * 1e3:9.2f} ms  batched evals {res['batched_evals']:5d}  "
                   f"{res['seed_evals'] / dt / 1e6:7.3f} M seed-evals/s"
                   + (f"  {res['iterations'] / dt / 1e3:8.1f} k iterations/s  best f {res['best_f']:.6e}"
-                     if "iterations" in res else ""), flush=True)
+                     if "iterations" in res else "")
+                  + (f"  failed line searches {res['ls_fails']} ({res['ls_fail_tick_share']:.1%} of the seed-ticks)"
+                     if "ls_fails" in res else ""), flush=True)
     info = eng.info()
     eng.close()
     a, b, c = (out[k]["wall_s"] for k in ("lockstep", "device", "bare"))
@@ -115,7 +126,7 @@ def run(cfg):
     out["lockstep_best_over_device_worst"] = min(a) / max(b)
     out["every_device_repeat_beats_best_lockstep"] = bool(max(b) < min(a))
     out["settings"] = dict(cfg=cfg, B=B, N=prob.N, Nt=prob.Nt, ns=Bs.shape[1], max_iter=MAX_ITER, outer_iters=OUTER,
-                           backward=info["backward"])
+                           order=ORDER, backward=info["backward"])
     print(f"{cfg}: tick / bare eval = " + " ".join(f"{r:.3f}" for r in out["device_over_bare"])
           + f"; best lockstep / worst device = {out['lockstep_best_over_device_worst']:.1f}; seed-ticks on done seeds "
           f"{out['device']['done_seed_tick_share']:.1%}", flush=True)
