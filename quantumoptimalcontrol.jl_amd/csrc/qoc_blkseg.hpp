@@ -26,6 +26,11 @@
 //            without halvings: closed form from the cos ω, sinc ω and e^{μ_k} e^{it} the propagator was formed from
 //            (sk2_contract_exact); otherwise the recurrence as a rolled loop to a term count chosen per seed in
 //            phase 0 (seg_contract_exact, blkseg_exact_terms).  Nothing else of the kernel depends on ORD.
+// Blocks of 2 rows whose control blocks have zero diagonals and no shifts (the cavity's class, ZD below) and no
+// halvings: U_k = z V_k with one unimodular constant z per block and V_k in SU(2), and both slice loops run on V_k
+// alone (sk2_form_v): phase 1 multiplies SU(2) matrices in 4 reals, phase 3 moves Ĝ = z̄ G (the same K_k), and the
+// traces need two of K's four Pauli components.  z enters once per lane: z^Nt on x_N (the only quantity of phase 2
+// that sees the phase), z̄ on G at the segment's end.
 // Neither x_k, λ_k nor U_k go to HBM: the launch reads u and writes J, the λ_N coefficients and dJdu.  qoc_get_states
 // and qoc_get_costates rebuild x_k / λ_k on demand with the k_blku_* chains (qoc_run_blk.hip).
 //
@@ -453,36 +458,28 @@ __device__ __forceinline__ void sk2_z(const Sk2& g0, const double* rec, double& 
   zi = fma(ph.x, st, ph.y * ct);
 }
 // Â = Ã_0 + u_1 Ã_1 + u_2 Ã_2 (no halvings) and U = e^{μ_k} exp(Â) in the closed form of seg_form (ph = e^{μ_k}).
-// ZD: the control generators' blocks have zero diagonals and no shifts, so Â's diagonal is Ã_0's and e^{μ_k} = e^{μ_0}
-// in every slice: z = e^{μ_k} e^{it} comes precomputed (ct0, st0: sk2_z, the same value)
 // EX (the exact contraction, sk2_contract_exact): also hands out ex = [cos ω, sinc ω, s3(ω), Re z, Im z], s3 from a
 // third Horner chain beside the two
-template <int K = BLKSEG_KMAX, bool ZD = false, bool EX = false>
+template <int K = BLKSEG_KMAX, bool EX = false>
 __device__ __forceinline__ void sk2_form(const Sk2 (&g)[3], double2 ph, double2 u, Sk2& ah, double (&ur)[4],
-                                         double (&ui)[4], double ct0 = 1.0, double st0 = 0.0, double a0 = 0.0,
-                                         double* ex = nullptr) {
+                                         double (&ui)[4], double* ex = nullptr) {
   constexpr BlksegTrig T = blkseg_trig();
-  if constexpr (ZD) {  // the same values (u_j times a zero diagonal adds nothing)
-    ah.d0 = g[0].d0;
-    ah.d1 = g[0].d1;
-  } else {
-    ah.d0 = fma(u.y, g[2].d0, fma(u.x, g[1].d0, g[0].d0));
-    ah.d1 = fma(u.y, g[2].d1, fma(u.x, g[1].d1, g[0].d1));
-  }
+  ah.d0 = fma(u.y, g[2].d0, fma(u.x, g[1].d0, g[0].d0));
+  ah.d1 = fma(u.y, g[2].d1, fma(u.x, g[1].d1, g[0].d1));
   ah.r = fma(u.y, g[2].r, fma(u.x, g[1].r, g[0].r));
   ah.q = fma(u.y, g[2].q, fma(u.x, g[1].q, g[0].q));
-  const double a = ZD ? a0 : 0.5 * (ah.d0 - ah.d1);  // (ZD: a0 the same value, once per lane)
+  const double a = 0.5 * (ah.d0 - ah.d1);
   const double w = fma(a, a, fma(ah.r, ah.r, ah.q * ah.q));
-  double cw = 0.0, sw = 0.0, s3 = 0.0, ct = ct0, st = st0;
+  double cw = 0.0, sw = 0.0, s3 = 0.0, ct, st;
 #pragma unroll
   for (int k = K; k >= 0; --k) {
     cw = fma(cw, w, T.c[k]);
     sw = fma(sw, w, T.s[k]);
     if constexpr (EX) s3 = fma(s3, w, T.d[k]);
   }
-  if constexpr (!ZD) sk2_phase<K>(ah.d0, ah.d1, ct, st);
-  // z = e^{μ_k} e^{it}; ZD (constant shifts too): the same in every slice, (ct0, st0) hold it
-  const double zr = ZD ? ct0 : ph.x * ct - ph.y * st, zi = ZD ? st0 : fma(ph.x, st, ph.y * ct);
+  sk2_phase<K>(ah.d0, ah.d1, ct, st);
+  // z = e^{μ_k} e^{it}
+  const double zr = ph.x * ct - ph.y * st, zi = fma(ph.x, st, ph.y * ct);
   const double cr = zr * cw, ci = zi * cw, sr = zr * sw, si = zi * sw;
   if constexpr (EX) {
     ex[0] = cw;
@@ -499,6 +496,59 @@ __device__ __forceinline__ void sk2_form(const Sk2 (&g)[3], double2 ph, double2 
   ui[1] = fma(sr, ah.q, si * ah.r);
   ur[2] = fma(-sr, ah.r, -si * ah.q);  // z sinc(ω) (-r + i q)
   ui[2] = fma(sr, ah.q, -si * ah.r);
+}
+// ZD: the control generators' blocks have zero diagonals and no shifts, and Re μ_0 = 0, so Â's diagonal is Ã_0's and
+// z = e^{μ_k} e^{it} is one unimodular constant of the lane's block (sk2_z) in every slice: U_k = z V_k with
+//   V_k = cos ω I + sinc ω (Â - i t I) = [[α, β], [-β̄, ᾱ]] in SU(2),  α = cos ω + i sinc ω a,  β = sinc ω (r + i q)
+// (a = a0, the block's constant half-difference).  The slice loops run on V alone, v = (Re α, Im α, Re β, Im β):
+// products of SU(2) matrices stay of that form in phase 1, and phase 3 moves Ĝ = z̄ G, for which K_k = U_k^H G_{k+1} =
+// V_k^H Ĝ_{k+1} (the same K) and Ĝ_k = K_k V_k.  z enters once per lane: z^Nt on x_N, z̄ on G at the segment's end.
+// EX: ex = [cos ω, sinc ω, s3(ω), Re z, Im z] as sk2_form's (zr, zi: the lane's z)
+template <int K = BLKSEG_KMAX, bool EX = false>
+__device__ __forceinline__ void sk2_form_v(const Sk2 (&g)[3], double2 u, double a0, Sk2& ah, double (&v)[4],
+                                           double zr = 1.0, double zi = 0.0, double* ex = nullptr) {
+  constexpr BlksegTrig T = blkseg_trig();
+  ah.d0 = g[0].d0;  // (u_j times a zero diagonal adds nothing)
+  ah.d1 = g[0].d1;
+  ah.r = fma(u.y, g[2].r, fma(u.x, g[1].r, g[0].r));
+  ah.q = fma(u.y, g[2].q, fma(u.x, g[1].q, g[0].q));
+  const double w = fma(a0, a0, fma(ah.r, ah.r, ah.q * ah.q));
+  double cw = 0.0, sw = 0.0, s3 = 0.0;
+#pragma unroll
+  for (int k = K; k >= 0; --k) {
+    cw = fma(cw, w, T.c[k]);
+    sw = fma(sw, w, T.s[k]);
+    if constexpr (EX) s3 = fma(s3, w, T.d[k]);
+  }
+  if constexpr (EX) {
+    ex[0] = cw;
+    ex[1] = sw;
+    ex[2] = s3;
+    ex[3] = zr;
+    ex[4] = zi;
+  }
+  v[0] = cw;
+  v[1] = sw * a0;
+  v[2] = sw * ah.r;
+  v[3] = sw * ah.q;
+}
+// the 2 x 2 matrix of v: [[α, β], [-β̄, ᾱ]] (negations only)
+__device__ __forceinline__ void sk2_expand(const double (&v)[4], double (&mr)[4], double (&mi)[4]) {
+  mr[0] = v[0];
+  mi[0] = v[1];
+  mr[1] = v[2];
+  mi[1] = v[3];
+  mr[2] = -v[2];
+  mi[2] = v[3];
+  mr[3] = v[0];
+  mi[3] = -v[1];
+}
+// p <- v p on SU(2) matrices in that form (p = (Re p, Im p, Re y, Im y)): p' = α p - β ȳ, y' = α y + β p̄
+__device__ __forceinline__ void sk2_vmul(const double (&v)[4], const double (&p)[4], double (&t)[4]) {
+  t[0] = fma(v[0], p[0], fma(-v[1], p[1], fma(-v[2], p[2], -v[3] * p[3])));
+  t[1] = fma(v[0], p[1], fma(v[1], p[0], fma(v[2], p[3], -v[3] * p[2])));
+  t[2] = fma(v[0], p[2], fma(-v[1], p[3], fma(v[2], p[0], v[3] * p[1])));
+  t[3] = fma(v[0], p[3], fma(v[1], p[2], fma(-v[2], p[1], v[3] * p[0])));
 }
 
 // R <- R X in place, X skew-Hermitian (x0, x1, yr + i yq): 12 FMAs per row instead of 16
@@ -571,6 +621,33 @@ __device__ __forceinline__ void sk2_contract_pauli(const Sk2& x, const double (&
   static_assert(ORD >= 1 && ORD <= 3, "Pauli form for orders 1..3");
   // doubled Pauli components of K: 2k0 = K00 + K11, 2k1 = K01 + K10, 2k2 = i (K01 - K10), 2k3 = K00 - K11
   const double k0i = Ki[0] + Ki[3], k1i = Ki[1] + Ki[2], k2i = Kr[1] - Kr[2], k3i = Ki[0] - Ki[3];
+  if constexpr (CX) {
+    // zero-diagonal controls without shifts: a1[0] = a1[3] = a2[0] = a2[3] = 0 exactly, so m0 and m3 (and Re d, 2 Re k3
+    // and al0, which feed nothing else) are not formed: they entered the sums as products with exact zeros added to
+    // finite values, so the traces are the same bits
+    double m1, m2;
+    if constexpr (ORD == 1) {
+      m1 = k1i;
+      m2 = k2i;
+    } else {
+      const double k0r = Kr[0] + Kr[3], k1r = Kr[1] + Kr[2], k2r = Ki[2] - Ki[1];
+      const double x1 = x.q, x2 = x.r;
+      if constexpr (ORD == 2) {
+        m1 = fma(x0c, k1r, fma(k0r, x1, k1i));
+        m2 = fma(x0c, k2r, fma(k0r, x2, k2i));
+      } else {
+        const double di = fma(x3c, k3i, fma(x2, k2i, x1 * k1i));
+        const double w = fma(x3c, x3c, fma(x2, x2, x1 * x1));
+        const double al1 = fma(-0.5, x02c, fma(-1.0 / 6.0, w, 1.0));
+        const double c = fma(-x0c, k0i, fma(-1.0 / 3.0, di, k0r));
+        m1 = fma(al1, k1i, fma(x0c, k1r, c * x1));
+        m2 = fma(al1, k2i, fma(x0c, k2r, c * x2));
+      }
+    }
+    acc1 = -0.5 * fma(a1[2], m2, a1[1] * m1);
+    acc2 = -0.5 * fma(a2[2], m2, a2[1] * m1);
+    return;
+  }
   double m0, m1, m2, m3;  // 2 Im m
   if constexpr (ORD == 1) {
     m0 = k0i;
@@ -624,15 +701,20 @@ __device__ __forceinline__ void sk2_contract_exact(const Sk2& x, const double (&
   const double x1 = x.q, x2 = x.r, x3 = CX ? x3c : 0.5 * (x.d0 - x.d1);
   const double dr = fma(x3, k3r, fma(x2, k2r, x1 * k1r)), di = fma(x3, k3i, fma(x2, k2i, x1 * k1i));
   // n = M / z (doubled, like K): n0 = cos ω k0 + i sinc ω d, n = sinc ω k + c x with c = i sinc ω k0 - s3 d
-  const double n0r = fma(cw, k0r, -sw * di), n0i = fma(cw, k0i, sw * dr);
   const double cr = -fma(sw, k0i, s3 * dr), ci = fma(sw, k0r, -s3 * di);
   // 2 Im m = Re z Im n + Im z Re n
-  const double m0 = fma(zr, n0i, zi * n0r);
   const double m1 = fma(zr, fma(sw, k1i, ci * x1), zi * fma(sw, k1r, cr * x1));
   const double m2 = fma(zr, fma(sw, k2i, ci * x2), zi * fma(sw, k2r, cr * x2));
-  const double m3 = fma(zr, fma(sw, k3i, ci * x3), zi * fma(sw, k3r, cr * x3));
-  acc1 = -0.5 * fma(a1[3], m3, fma(a1[2], m2, fma(a1[1], m1, a1[0] * m0)));
-  acc2 = -0.5 * fma(a2[3], m3, fma(a2[2], m2, fma(a2[1], m1, a2[0] * m0)));
+  if constexpr (CX) {  // a1[0] = a1[3] = a2[0] = a2[3] = 0 exactly (sk2_contract_pauli): n0, m0 and m3 are not formed
+    acc1 = -0.5 * fma(a1[2], m2, a1[1] * m1);
+    acc2 = -0.5 * fma(a2[2], m2, a2[1] * m1);
+  } else {
+    const double n0r = fma(cw, k0r, -sw * di), n0i = fma(cw, k0i, sw * dr);
+    const double m0 = fma(zr, n0i, zi * n0r);
+    const double m3 = fma(zr, fma(sw, k3i, ci * x3), zi * fma(sw, k3r, cr * x3));
+    acc1 = -0.5 * fma(a1[3], m3, fma(a1[2], m2, fma(a1[1], m1, a1[0] * m0)));
+    acc2 = -0.5 * fma(a2[3], m3, fma(a2[2], m2, fma(a2[1], m1, a2[0] * m0)));
+  }
 }
 
 // ---- the exact traces on the generic path (blocks of 3 rows; blocks of 2 rows with halvings) ----
@@ -783,9 +865,12 @@ __device__ __forceinline__ void seg_pen_acc(int pm, const double (&vr)[NB * NB],
 // One slice of the penalty in phase 3, D in LDS (entry e at dp[e stride]): G += f D Π on the penalised columns of D
 // (the source 2 μ x_k[P, C] of λ_k in G_k = Σ_c x_k λ_k^H), then D <- U^H D U.  D is read column by column (T = D U
 // accumulated) and written back row by row (U^H T), so that beside U and G only T is live.
-template <int NB>
+// CF: the factor is complex, f + i fi (the phase-free loops: G stands for Ĝ = z̄ G, the source becomes z̄ 2 μ D Π, and
+// U for V, which conjugates D as U does)
+template <int NB, bool CF = false>
 __device__ __forceinline__ void seg_pen_step(int pm, double f, double2* dp, int stride, const double (&ur)[NB * NB],
-                                             const double (&ui)[NB * NB], double (&gr)[NB * NB], double (&gi)[NB * NB]) {
+                                             const double (&ui)[NB * NB], double (&gr)[NB * NB], double (&gi)[NB * NB],
+                                             double fi = 0.0) {
   double tr[NB * NB], ti[NB * NB];
 #pragma unroll
   for (int e = 0; e < NB * NB; ++e) tr[e] = ti[e] = 0.0;
@@ -797,8 +882,13 @@ __device__ __forceinline__ void seg_pen_step(int pm, double f, double2* dp, int 
     if ((pm >> q) & 1) {
 #pragma unroll
       for (int a = 0; a < NB; ++a) {
-        gr[a * NB + q] = fma(f, c[a].x, gr[a * NB + q]);
-        gi[a * NB + q] = fma(f, c[a].y, gi[a * NB + q]);
+        if constexpr (CF) {
+          gr[a * NB + q] = fma(f, c[a].x, fma(-fi, c[a].y, gr[a * NB + q]));
+          gi[a * NB + q] = fma(f, c[a].y, fma(fi, c[a].x, gi[a * NB + q]));
+        } else {
+          gr[a * NB + q] = fma(f, c[a].x, gr[a * NB + q]);
+          gi[a * NB + q] = fma(f, c[a].y, gi[a * NB + q]);
+        }
       }
     }
 #pragma unroll
@@ -1050,13 +1140,59 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
   // the control generators' blocks without diagonal (cavity, zz: drives between levels): Â's diagonal is Ã_0's in
   // every slice, so e^{it} of the block's mean diagonal is computed once per lane (uniform over the workgroup)
   const bool zdl = NB != 2 || (gk[1].d0 == 0.0 && gk[1].d1 == 0.0 && gk[2].d0 == 0.0 && gk[2].d1 == 0.0);
-  const bool zd = __syncthreads_and(zdl ? 1 : 0) != 0 && cmu;
+  // With Re μ_0 = 0 besides (skew-Hermitian generators: always), z = e^{μ_0} e^{it} is one unimodular constant per
+  // lane and the fast path's loops run phase-free on SU(2) (sk2_form_v); otherwise the general 2-row form runs, which
+  // computes the same z in every slice.
+  const bool zd = __syncthreads_and(zdl ? 1 : 0) != 0 && cmu && sp.mur[0] == 0.0;
   const double za0 = NB == 2 ? 0.5 * (gk[0].d0 - gk[0].d1) : 0.0;  // ZD: the blocks' constant half-difference
-  auto p1_fast = [&](int jj, auto SEL_, auto K_, auto ZD_, double ct0, double st0) {
+  // the fast path's series degree (uniform per seed: one loop instance per degree class)
+  const int ksel = __builtin_amdgcn_readfirstlane(blkseg_series_k(rmax * s0));
+  // ZD on the fast path: the running product of phase 1 as (p, y) of [[p, y], [-ȳ, p̄]], and the lane's z (formed where
+  // it is used, for x_N and before phase 3, the same value both times: not live across the loops)
+  const bool su = fast && zd;
+  double pq[4] = {1.0, 0.0, 0.0, 0.0};
+  auto lane_z = [&](double& zr, double& zi) {
+    zr = 1.0;
+    zi = 0.0;
+    if constexpr (NB == 2) {
+      if (su) {
+        if (ksel == 5) sk2_z<5>(gk[0], rec, zr, zi);
+        else if (ksel == 7) sk2_z<7>(gk[0], rec, zr, zi);
+        else sk2_z<BLKSEG_KMAX>(gk[0], rec, zr, zi);
+      }
+    }
+  };
+  auto p1_fast = [&](int jj, auto SEL_, auto K_, auto ZD_) {
     constexpr bool SEL = decltype(SEL_)::value;
     constexpr int KS = decltype(K_)::value;
     constexpr bool ZD = decltype(ZD_)::value;
     if constexpr (NB == 2) {
+    if constexpr (ZD) {
+      double vv[2][4];
+      bool act[2];
+#pragma unroll
+      for (int v = 0; v < 2; ++v) {
+        const int k = kb + jj + v;
+        act[v] = !SEL || (sact && jj + v < L && k < ke);
+        const double* r = rec + 4 * (size_t)(act[v] ? k : 0);
+        Sk2 ah;
+        sk2_form_v<KS>(gk, *reinterpret_cast<const double2*>(r + 2), za0, ah, vv[v]);
+      }
+#pragma unroll
+      for (int v = 0; v < 2; ++v) {
+        double t[4];
+        sk2_vmul(vv[v], pq, t);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) pq[e] = !SEL || act[v] ? t[e] : pq[e];
+        if constexpr (PEN) {
+          if (pm && (!SEL || act[v])) {
+            double wr_[4], wi_[4];
+            sk2_expand(pq, wr_, wi_);
+            seg_pen_acc<NB>(pm, wr_, wi_, Hr, Hi);
+          }
+        }
+      }
+    } else {
       double ur[2][4], ui[2][4];
       bool act[2];
 #pragma unroll
@@ -1065,8 +1201,8 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
         act[v] = !SEL || (sact && jj + v < L && k < ke);
         const double* r = rec + 4 * (size_t)(act[v] ? k : 0);
         Sk2 ah;
-        sk2_form<KS, ZD>(gk, *reinterpret_cast<const double2*>(r), *reinterpret_cast<const double2*>(r + 2), ah, ur[v],
-                         ui[v], ct0, st0, za0);
+        sk2_form<KS>(gk, *reinterpret_cast<const double2*>(r), *reinterpret_cast<const double2*>(r + 2), ah, ur[v],
+                     ui[v]);
       }
 #pragma unroll
       for (int v = 0; v < 2; ++v) {
@@ -1082,18 +1218,19 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
         }
       }
     }
+    }  // NB == 2
   };
-  // the fast path's series degree (uniform per seed: one loop instance per degree class)
-  const int ksel = __builtin_amdgcn_readfirstlane(blkseg_series_k(rmax * s0));
   auto loop1z = [&](auto K_, auto ZD_) {
-    constexpr int KS = decltype(K_)::value;
-    double ct0 = 1.0, st0 = 0.0;
-    if constexpr (NB == 2 && decltype(ZD_)::value) sk2_z<KS>(gk[0], rec, ct0, st0);
     for (int jj = 0; jj < L; jj += 2) {
       if (turns) seg_turn(grp, ngrp, jj >> 1);
       sprog.step(jj >> 1);
-      if (jj + 1 < Lf) p1_fast(jj, std::false_type(), K_, ZD_, ct0, st0);
-      else p1_fast(jj, std::true_type(), K_, ZD_, ct0, st0);
+      if (jj + 1 < Lf) p1_fast(jj, std::false_type(), K_, ZD_);
+      else p1_fast(jj, std::true_type(), K_, ZD_);
+    }
+    // ZD: the segment product without its phase z^(ke - kb), as a matrix for phase 2 (negations only); everything
+    // there but x_N is invariant to the phase
+    if constexpr (NB == 2) {
+      if constexpr (decltype(ZD_)::value) sk2_expand(pq, qr, qi);
     }
   };
   auto loop1 = [&](auto K_) {
@@ -1270,6 +1407,22 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
   // x_N = Q_{S-1} x_0 on each block (the last segment's lanes), in place in xN
   const bool last = sact && s == S - 1;
   if (last) {
+    // ZD: the block's phase over all slices, z^Nt by square-and-multiply (x_N is the one quantity that sees it)
+    double znr = 1.0, zni = 0.0;
+    if (su) {
+      double br, bi;
+      lane_z(br, bi);
+      for (int n = Nt; n > 0; n >>= 1) {
+        if (n & 1) {
+          const double t = znr * br - zni * bi;
+          zni = fma(znr, bi, zni * br);
+          znr = t;
+        }
+        const double t = br * br - bi * bi;
+        bi = 2.0 * (br * bi);
+        br = t;
+      }
+    }
     for (int c = 0; c < m; ++c) {
       double xr[NB], xi[NB];
 #pragma unroll
@@ -1285,6 +1438,11 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
         for (int q = 0; q < NB; ++q) {
           yr = fma(qr[i * NB + q], xr[q], fma(-qi[i * NB + q], xi[q], yr));
           yi = fma(qr[i * NB + q], xi[q], fma(qi[i * NB + q], xr[q], yi));
+        }
+        if (su) {
+          const double t = yr * znr - yi * zni;
+          yi = fma(yr, zni, yi * znr);
+          yr = t;
         }
         if (brw[i] >= 0) {
           const size_t o = 2 * ((size_t)c * N + brw[i]);
@@ -1557,6 +1715,22 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
   auto pen_step = [&](const double (&ur)[E], const double (&ui)[E]) {
     seg_pen_step<NB>(pm, pen2, slot + (size_t)opaque(s) * E * nblk + beta, nblk, ur, ui, Gr, Gi);
   };
+  // ZD on the fast path: the loop moves Ĝ = z̄ G (sk2_form_v), from here on in Gr, Gi; the fused launch and the
+  // backward half (G back from HBM) do the same operations on the same G.  The penalty's source turns with it.
+  double zr, zi;
+  lane_z(zr, zi);
+  if (su) {
+#pragma unroll
+    for (int e = 0; e < E; ++e) {
+      const double t = fma(zr, Gr[e], zi * Gi[e]);
+      Gi[e] = fma(zr, Gi[e], -zi * Gr[e]);
+      Gr[e] = t;
+    }
+  }
+  const double pen2r = pen2 * zr, pen2i = -pen2 * zi;
+  auto pen_step_v = [&](const double (&ur)[E], const double (&ui)[E]) {
+    seg_pen_step<NB, true>(pm, pen2r, slot + (size_t)opaque(s) * E * nblk + beta, nblk, ur, ui, Gr, Gi, pen2i);
+  };
   double* const wr = wred + 128 * RB * w;
   // the slices' sums over their blocks: each step's partial sums go to slot (L - 1 - jj) % RB of a wave-private
   // area; every RB steps (and after the last) one lane per (step, segment of the wave, control) adds its nblk
@@ -1590,7 +1764,7 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
     sk2_pauli2(Sk2{gk[1].d0 + mu1i, gk[1].d1 + mu1i, gk[1].r, gk[1].q}, pa1);
     sk2_pauli2(Sk2{gk[2].d0 + mu2i, gk[2].d1 + mu2i, gk[2].r, gk[2].q}, pa2);
   }
-  auto p3_fast = [&](int jj, auto SEL_, auto K_, auto ZD_, double ct0, double st0) {
+  auto p3_fast = [&](int jj, auto SEL_, auto K_, auto ZD_) {
     constexpr bool SEL = decltype(SEL_)::value;
     constexpr int KS = decltype(K_)::value;
     constexpr bool ZD = decltype(ZD_)::value;
@@ -1601,12 +1775,21 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
       const double2 u = *reinterpret_cast<const double2*>(r + 2);
       Sk2 ah;
       double ur[4], ui[4], ex[5];
-      sk2_form<KS, ZD, ORD == 0>(gk, *reinterpret_cast<const double2*>(r), u, ah, ur, ui, ct0, st0, za0, ex);
+      if constexpr (ZD) {  // V_k as a matrix (negations only) and Ĝ in Gr, Gi: the same K_k
+        double vv[4];
+        sk2_form_v<KS, ORD == 0>(gk, u, za0, ah, vv, zr, zi, ex);
+        sk2_expand(vv, ur, ui);
+      } else {
+        sk2_form<KS, ORD == 0>(gk, *reinterpret_cast<const double2*>(r), u, ah, ur, ui, ex);
+      }
       if constexpr (PEN) {
         // G_{k+1} takes the source of λ_{k+1}, 2 μ D_{k+1} Π; then D_k = U_k^H D_{k+1} U_k
-        if (pm && (!SEL || act)) pen_step(ur, ui);
+        if (pm && (!SEL || act)) {
+          if constexpr (ZD) pen_step_v(ur, ui);
+          else pen_step(ur, ui);
+        }
       }
-      // K_k = U_k^H G_{k+1}, G_k = K_k U_k
+      // K_k = U_k^H G_{k+1}, G_k = K_k U_k (ZD: K_k = V_k^H Ĝ_{k+1}, Ĝ_k = K_k V_k)
       double Kr[4], Ki[4], tr[4], ti[4];
       seg_mm<2, true, false>(ur, ui, Gr, Gi, Kr, Ki);
       seg_mm<2, false, false>(Kr, Ki, ur, ui, tr, ti);
@@ -1633,14 +1816,11 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
     }
   };
   auto loop3z = [&](auto K_, auto ZD_) {
-    constexpr int KS = decltype(K_)::value;
-    double ct0 = 1.0, st0 = 0.0;
-    if constexpr (NB == 2 && decltype(ZD_)::value) sk2_z<KS>(gk[0], rec, ct0, st0);
     for (int jj = L - 1; jj >= 0; --jj) {
       if (turns) seg_turn(grp, ngrp, jj);
       sprog.step(L + (L - 1 - jj));
-      if (jj < Lf) p3_fast(jj, std::false_type(), K_, ZD_, ct0, st0);
-      else p3_fast(jj, std::true_type(), K_, ZD_, ct0, st0);
+      if (jj < Lf) p3_fast(jj, std::false_type(), K_, ZD_);
+      else p3_fast(jj, std::true_type(), K_, ZD_);
     }
   };
   auto loop3 = [&](auto K_) {
