@@ -59,7 +59,7 @@
 // co-states' rebuild (blku_costates) adds the sources from rebuilt states.  Lanes of blocks without a row in P skip
 // all of it (uniform control flow apart).  Extra LDS: D_0 per block.  Blocks of 3 rows: the fused penalised kernel
 // does not fit 256 VGPRs (it spills), so the host runs the penalised eval as BLKSEG_FWD + BLKSEG_BWD, which do
-// (qoc_run_blk.hip blkseg_eval), and BLKSEG_FUSED with PEN is built for blocks of 2 rows only.
+// (qoc_run_blkseg.hip blkseg_eval), and BLKSEG_FUSED with PEN is built for blocks of 2 rows only.
 #pragma once
 #include "qoc_blku.hpp"
 

@@ -149,8 +149,9 @@ __device__ __forceinline__ int wave_max(int v) {
 // largest J and P among them).  J: the fewest halvings with ρ_k / 2^J <= θ_cap; P: the smallest degree whose tail
 // bound b^{P+1} / (P+1)! / (1 - b / (P+2)) >= Σ_{t>P} b^t / t! is <= 2^-53 (b = ρ_k / 2^J < 1).
 // rec = [Re e^{μ_k}, Im e^{μ_k}, 2^-J, 2^-J u_1k, 2^-J u_2k, P, J, 0]; terms += Σ P 2^J (executed Taylor terms).
-__global__ __launch_bounds__(256) void k_blku_rec(const BlkuParams bp, const double* __restrict__ u, int nu, int Nt,
-                                                  long long total, double* __restrict__ rec) {
+// (static: a non-template kernel in a header)
+static __global__ __launch_bounds__(256) void k_blku_rec(const BlkuParams bp, const double* __restrict__ u, int nu,
+                                                         int Nt, long long total, double* __restrict__ rec) {
   const long long t = (long long)blockIdx.x * blockDim.x + threadIdx.x;
   const long long tt = t < total ? t : 0;
   const int b = (int)(tt / bp.Ntp), k = (int)(tt - (long long)b * bp.Ntp);

@@ -9,6 +9,7 @@
 //   qoc_run_big.hip       the large-N GEMM pipeline, the GEMM-shaped gradient and the Fréchet gradient
 //   qoc_run_ode.hip       the Tsit5 path
 //   qoc_run_blk.hip       the block chains and block gradient (generators with small invariant blocks)
+//   qoc_run_blkseg.hip    the segmented block eval (blocks of <= 3 rows: one launch for J and dJdu)
 // Each kernel template is launched from one translation unit only; the context (qoc_ctx) and the entry points
 // between the units are declared here.
 #pragma once
@@ -31,7 +32,7 @@
 
 using namespace qoc;
 
-// launch shape of the segmented block eval (qoc_run_blk.hip blkseg_shape)
+// launch shape of the segmented block eval (qoc_run_blkseg.hip blkseg_shape)
 struct BlksegShape {
   int W, S, L, UPW, RB;
   size_t lds;
@@ -381,20 +382,22 @@ int blk_forward(qoc_ctx* c);
 int blk_backward(qoc_ctx* c, int order, double* d_dJdu);
 bool blk_concurrent_ok(const qoc_ctx* c, int order);
 int blk_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu);
+int blku_states(qoc_ctx* c);      // rebuild x_k after a segmented eval (no-op unless X_lazy)
+// the reference's split call form for blocks of 5..16 rows on stored propagators: propagate = formation + forward
+// chain (1: not applicable), grape_sensitivity = the μ recurrence + the order-3 gradient
+int blkp_forward(qoc_ctx* c);
+bool blkp_backward_ok(const qoc_ctx* c, int order);
+int blkp_backward(qoc_ctx* c, double* d_dJdu, const int* stale);
+int blk_materialize(qoc_ctx* c);  // rebuild every lazily kept x_k / λ_k (before a setter changes what they need)
+
+// ---- qoc_run_blkseg.hip ----
 // the segmented block eval (qoc_blkseg.hpp): one launch for J and dJdu, x_k / λ_k rebuilt on demand
 bool blkseg_ok(const qoc_ctx* c, int order);
 int blkseg_eval(qoc_ctx* c, int order, const double* d_u, double* d_J, double* d_dJdu);
-int blku_states(qoc_ctx* c);      // rebuild x_k after a segmented eval (no-op unless X_lazy)
 // the reference's split call form on the segmented eval: propagate = phases 0-2 (G at the segment ends to HBM),
 // grape_sensitivity = phase 3 (stale: the device flag of a stale-u check queued before it, or nullptr)
 bool blkseg_split_ok(const qoc_ctx* c);
 int blkseg_forward(qoc_ctx* c, const double* d_u, double* d_J);
 int blkseg_backward(qoc_ctx* c, int order, double* d_dJdu, const int* stale);
-// the same for blocks of 5..16 rows on stored propagators: propagate = formation + forward chain (1: not applicable),
-// grape_sensitivity = the μ recurrence + the order-3 gradient
-int blkp_forward(qoc_ctx* c);
-bool blkp_backward_ok(const qoc_ctx* c, int order);
-int blkp_backward(qoc_ctx* c, double* d_dJdu, const int* stale);
-int blk_materialize(qoc_ctx* c);  // rebuild every lazily kept x_k / λ_k (before a setter changes what they need)
 
 }  // namespace qoc_host

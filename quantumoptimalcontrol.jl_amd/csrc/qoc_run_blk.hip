@@ -4,8 +4,8 @@
 #include <numeric>
 
 #include "qoc_blk.hpp"
+#include "qoc_blk_host.hpp"
 #include "qoc_blkp.hpp"
-#include "qoc_blkseg.hpp"
 #include "qoc_blku.hpp"
 #include "qoc_internal.hpp"
 
@@ -310,16 +310,6 @@ static int blku_records(qoc_ctx* c, BlkuParams& bp, bool count, const double* d_
   mark_end(c, mk);
   HIPCHK(c, hipGetLastError());
   return QOC_OK;
-}
-
-static BlkArgs blk_args(const qoc_ctx* c) {
-  BlkArgs bk{};
-  bk.brow = c->d_brow;
-  bk.A = c->d_A;
-  bk.nblk = c->nblk;
-  bk.wrow = c->d_wrow;
-  bk.nwb = c->nwb;
-  return bk;
 }
 
 static int blk_threads(const qoc_ctx* c, int nwb = -1) {
@@ -1443,18 +1433,6 @@ static hipError_t blku_dispatch(const qoc_ctx* c, F&& f) {
   return hipErrorInvalidValue;
 }
 
-// the gradient order 1..4 as a compile-time constant
-template <typename F>
-static hipError_t blk_order_dispatch(int order, F&& f) {
-  using std::integral_constant;
-  switch (order) {
-    case 1: return f(integral_constant<int, 1>());
-    case 2: return f(integral_constant<int, 2>());
-    case 3: return f(integral_constant<int, 3>());
-    default: return f(integral_constant<int, 4>());
-  }
-}
-
 // the prefix-product group size as a compile-time constant (1, or 2 for blocks of <= 3 rows)
 template <int NB, typename F>
 static hipError_t blku_sdispatch(int S, F&& f) {
@@ -1684,310 +1662,6 @@ static int blku_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu) {
   }
   if (r) return r;
   c->L_is_mu = false;
-  return QOC_OK;
-}
-
-// ---- segmented block eval (qoc_blkseg.hpp) -------------------------------------------------------------------------
-// One workgroup per seed with W waves (8 at one seed per CU, fewer when several seeds share a CU: 8 wave slots at the
-// kernel's <= 256 VGPRs), UPW = 64 / nblk segments per wave, S = W UPW segments of L = ceil(Nt / S) slices (then S
-// trimmed so that no segment is empty).  QOC_BLKSEG_W / QOC_BLKSEG_S override the waves / cap the segments.
-// Derived once per context and again when one of its inputs changes (qoc_ctx::seg_key): every eval asks for it, some
-// twice, and the B = 1 plumbing latency is host time.  The sizes are compared here, not invalidated by their setters:
-// m moves with the state packing and the blocks with every qoc_set_generators, and a missed setter would launch a
-// stale shape.  The cache is the context's (mutable members: blkseg_ok, a predicate on a const context, fills it
-// too); like the rest of a context it is for one host thread at a time.  The reference returned stays valid until
-// the next call with other sizes.
-// The state penalty in the form the segmented eval takes (BlksegParams::prow / pcol): whether the eval is a penalised
-// one (μ != 0 with at least one row and one column; otherwise the unpenalised kernel computes the same J and dJdu).
-// The masks are the context's, derived on first use after qoc_set_state_penalty or a new block layout dropped them.
-static bool blkseg_pen(const qoc_ctx* c) {
-  if (c->mu == 0.0) return false;
-  if (!c->seg_pen_valid) {
-    c->seg_prow[0] = c->seg_prow[1] = c->seg_prow[2] = 0;
-    c->seg_pcol = 0;
-    const int NB = c->blk_nb;
-    if (NB >= 2 && NB <= 3 && c->nblk <= 32 && (int)c->h_brow.size() == c->nblk * NB)
-      for (int r : c->h_pen_rows)
-        for (int q = 0; q < c->nblk * NB; ++q)
-          if (c->h_brow[q] == r) c->seg_prow[q % NB] |= 1u << (q / NB);
-    for (int col : c->h_pen_cols)
-      if (col >= 0 && col < 32) c->seg_pcol |= 1u << col;
-    c->seg_pen_valid = true;
-  }
-  return (c->seg_prow[0] | c->seg_prow[1] | c->seg_prow[2]) != 0 && c->seg_pcol != 0;
-}
-
-static const BlksegShape& blkseg_shape(const qoc_ctx* c) {
-  const bool pen = blkseg_pen(c);
-  const int key[8] = {c->B, c->Nt, c->N, c->m, c->nu, c->blk_nb, c->nblk, pen ? 1 : 0};
-  if (std::equal(key, key + 8, c->seg_key)) return c->seg_shape;
-  BlksegShape& s = c->seg_shape;
-  s = BlksegShape{};
-  const int per_cu = std::max(1, std::min(8, (c->B + c->ncu - 1) / std::max(1, c->ncu)));
-  s.W = std::max(1, 8 / per_cu);
-  if (const char* env = getenv("QOC_BLKSEG_W")) s.W = std::max(1, std::min(8, atoi(env)));
-  s.UPW = 64 / std::max(1, c->nblk);
-  int S = std::max(1, std::min(s.W * s.UPW, c->Nt));
-  if (const char* env = getenv("QOC_BLKSEG_S")) S = std::max(1, std::min(S, atoi(env)));
-  s.L = (c->Nt + S - 1) / S;
-  s.S = (c->Nt + s.L - 1) / s.L;
-  s.W = (s.S + s.UPW - 1) / s.UPW;
-  s.RB = blkseg_rb(s.UPW, c->nu);
-  // blocks of 2 rows: up to 8 slice-steps per reduction when the LDS holds them (cavity: 0.0727 -> 0.0715 ms per launch,
-  // the same sums in the same order, profiles/bench_r06zl_*); QOC_BLKSEG_RB overrides (up to 64 / (UPW nu))
-  const int rbmax = std::max(1, 64 / (s.UPW * std::max(1, c->nu)));
-  if (c->blk_nb == 2) {
-    const int rb8 = std::min(8, rbmax);
-    if (blkseg_lds(c->N, c->m, c->nu, c->blk_nb, c->nblk, c->Nt, s.S, s.W, rb8, pen) <= BLKSEG_LDS_MAX) s.RB = rb8;
-  }
-  if (const char* e = getenv("QOC_BLKSEG_RB")) s.RB = std::max(1, std::min(atoi(e), rbmax));
-  s.lds = blkseg_lds(c->N, c->m, c->nu, c->blk_nb, c->nblk, c->Nt, s.S, s.W, s.RB, pen);
-  std::copy(key, key + 8, c->seg_key);
-  return s;
-}
-
-// The segmented eval applies to block propagators of blocks of <= 3 rows with exactly skew-Hermitian generators
-// (unitary slices), the built-in costs with or without the state penalty (the kernel's PEN instantiations;
-// QOC_BLKSEG_PEN=0 leaves a penalised eval to the k_blku_* chains) and no co-state source (an arbitrary dL/dx needs
-// x_k); QOC_BLKSEG=0 keeps the forward + fused backward of k_blku_*.  The exact (Fréchet) gradient is the kernel's
-// ORD 0 instantiation (the whole series of the contraction); QOC_BLKSEG_EXACT=0 leaves an exact eval to the rebuilt
-// x_k / λ_k and the dense Fréchet kernel (dense_gradient), the second implementation the tests compare against.
-bool blkseg_ok(const qoc_ctx* c, int order) {
-  if (!blku_on(c) || (c->blk_nb != 2 && c->blk_nb != 3) || !c->skew_exact || c->nblk > 32) return false;
-  const bool exact = order == QOC_DUKDP_EXACT;
-  if ((!exact && (order < 1 || order > BLK_ORDMAX)) || c->src_on) return false;
-  if (exact) {
-    const char* xe = getenv("QOC_BLKSEG_EXACT");
-    if (xe && !std::strcmp(xe, "0")) return false;
-  }
-  if (c->cost_kind != QOC_COST_TRACE && c->cost_kind != QOC_COST_ZCAL) return false;
-  const char* env = getenv("QOC_BLKSEG");
-  if (env && !std::strcmp(env, "0")) return false;
-  if (c->mu != 0.0) {
-    const char* pe = getenv("QOC_BLKSEG_PEN");
-    if ((pe && !std::strcmp(pe, "0")) || c->m > 32) return false;  // (the column mask has 32 bits)
-  }
-  return blkseg_shape(c).lds <= BLKSEG_LDS_MAX;
-}
-
-// (the exact tag has its own dispatch: blk_order_dispatch and BLK_ORDMAX stay the Taylor orders' alone, so the
-// k_blku_*, k_blkp_* and dense kernels keep refusing or routing QOC_DUKDP_EXACT as before)
-template <typename F>
-static hipError_t blkseg_dispatch(int NB, int order, F&& f) {
-  if (order == QOC_DUKDP_EXACT) {
-    const std::integral_constant<int, 0> ex;
-    if (NB == 2) return f(std::integral_constant<int, 2>(), ex);
-    return f(std::integral_constant<int, 3>(), ex);
-  }
-  return blk_order_dispatch(order, [&](auto ORD_) {
-    if (NB == 2) return f(std::integral_constant<int, 2>(), ORD_);
-    return f(std::integral_constant<int, 3>(), ORD_);
-  });
-}
-
-static int ensure_lazy_bufs(qoc_ctx* c) {
-  const size_t nu_t = (size_t)c->B * c->nu * c->Nt, ncf = (size_t)c->B * 2 * c->m_user;
-  if (!c->d_u_lam) {
-    HIPCHK(c, hipMalloc((void**)&c->d_u_lam, nu_t * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->d_coef_lam, ncf * sizeof(cx<double>)));
-    c->dev_bytes += nu_t * sizeof(double) + ncf * sizeof(cx<double>);
-  }
-  return QOC_OK;
-}
-
-// the launch parameters every mode shares; the best-(J, seed) epilogue's buffers on first use
-static int blkseg_params(qoc_ctx* c, const BlksegShape& s, BlksegParams& sp) {
-  sp = BlksegParams{};
-  for (int j = 0; j < 3; ++j) {
-    const bool on = j <= c->nu;
-    sp.rad[j] = on ? c->tprm.rad[j] : 0.0;  // skew-Hermitian: spectral half-widths of the shifted generators
-    sp.mur[j] = on ? c->tprm.mur[j] : 0.0;
-    sp.mui[j] = on ? c->tprm.mui[j] : 0.0;
-  }
-  sp.theta_cap = c->tprm.theta[17];
-  sp.S = s.S;
-  sp.L = s.L;
-  sp.UPW = s.UPW;
-  sp.RB = s.RB;
-  sp.gtab = c->d_gtab;
-  sp.terms = c->d_terms;
-  if (blkseg_pen(c)) {  // (else zeros: the unpenalised kernel reads none of them)
-    sp.pen_mu = c->mu;
-    for (int i = 0; i < 3; ++i) sp.prow[i] = c->seg_prow[i];
-    sp.pcol = c->seg_pcol;
-  }
-  // the best (J, seed) for qoc_allgather_best_dev, found by the launch's last workgroup
-  if (!c->d_best) {  // no communicator yet: this context alone (the epilogue's own layout)
-    HIPCHK(c, hipMalloc((void**)&c->d_best, 6 * sizeof(double)));
-    c->world = 1;
-    c->rank = 0;
-  }
-  if (!c->d_done) {
-    HIPCHK(c, hipMalloc((void**)&c->d_done, sizeof(unsigned int)));
-    HIPCHK(c, hipMemsetAsync(c->d_done, 0, sizeof(unsigned int), c->stream));
-  }
-  sp.done = c->d_done;
-  sp.best = c->d_best + 2 + 2 * c->rank;
-  sp.seed_offset = c->seed_offset;
-  // one rank: the pick after the (identity) exchange is done here, when a buffer is registered
-  const bool direct = c->world == 1 && c->best_out;
-  sp.best_res = direct ? c->d_best + 2 + 2 * c->world : nullptr;
-  sp.best_out = direct ? c->best_out : nullptr;
-  c->best_direct = direct;
-  return QOC_OK;
-}
-
-// blk_lds_attr for the segmented eval's kernels without a runtime call per launch: a context sets a kernel's limit
-// once (seg_attr), to the most the eval ever asks for (BLKSEG_LDS_MAX less the kernel's static LDS) and not to its own
-// size, because the limit belongs to the kernel, not to the context: another context with a smaller shape must not
-// lower it
-static hipError_t blkseg_lds_attr(qoc_ctx* c, int nb, int ord, int mode, bool pen, const void* kern, size_t lds) {
-  bool& set = c->seg_attr[nb - 2][ord == 0 ? BLK_ORDMAX : ord - 1][mode][pen ? 1 : 0];  // (ORD 0: the exact slot)
-  if (lds <= 65536 || set) return hipSuccess;
-  hipFuncAttributes fa{};
-  hipError_t e = hipFuncGetAttributes(&fa, kern);
-  if (e != hipSuccess) return e;
-  e = hipFuncSetAttribute(kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)(BLKSEG_LDS_MAX - fa.sharedSizeBytes));
-  set = e == hipSuccess;
-  return e;
-}
-
-template <int MODE>
-static hipError_t blkseg_launch(qoc_ctx* c, int order, const BlksegShape& s, const BlksegParams& sp) {
-  const TChainArgs g = tchain_args(c);
-  const BlkArgs bk = blk_args(c);
-  return blkseg_dispatch(c->blk_nb, MODE == BLKSEG_FWD ? 1 : order, [&](auto NB_, auto ORD_) {
-    constexpr int NB = decltype(NB_)::value, ORD = decltype(ORD_)::value;
-    // the forward half has no gradient: one instantiation (ORD 1) serves every order
-    if constexpr (MODE == BLKSEG_FWD && ORD != 1) {
-      return hipErrorInvalidValue;
-    } else {
-      auto launch = [&](auto PEN_) {
-        constexpr bool PEN = decltype(PEN_)::value;
-        // blocks of 3 rows: the penalised eval runs as the forward and the backward half (blkseg_eval), so the fused
-        // penalised kernel, which does not fit its registers there, is never built
-        if constexpr (PEN && NB == 3 && MODE == BLKSEG_FUSED) {
-          return hipErrorInvalidValue;
-        } else {
-          auto kern = k_blkseg_eval<NB, ORD, 8, MODE, PEN>;
-          const hipError_t q = blkseg_lds_attr(c, NB, ORD, MODE, PEN, (const void*)kern, s.lds);
-          if (q != hipSuccess) return q;
-          hipLaunchKernelGGL(kern, dim3(c->B), dim3(64 * s.W), s.lds, c->stream, g, bk, sp);
-          return hipGetLastError();
-        }
-      };
-      // the penalised instantiation when the launch carries a penalty (blkseg_params)
-      if (sp.pen_mu != 0.0) return launch(std::true_type());
-      return launch(std::false_type());
-    }
-  });
-}
-
-int blkseg_eval(qoc_ctx* c, int order, const double* d_u, double* d_J, double* d_dJdu) {
-  if (blkseg_pen(c) && c->blk_nb == 3) {
-    // Blocks of 3 rows with the penalty: the two halves as two launches (G and D at the segment ends through HBM).
-    // In one kernel the penalised phases 1-2 and phase 3 together spill (416 bytes per lane at order 3), and the two
-    // launches measured faster than that kernel (zz, B = 512: 4.4M against 4.0M evals/s); J and dJdu are bitwise the
-    // same, and each half is within its registers.  The eval leaves no split forward behind.
-    int r = blkseg_forward(c, d_u, d_J);
-    if (r) return r;
-    c->fwd_kind = 0;
-    c->props_since_reset--;  // (counted by the caller)
-    return blkseg_backward(c, order, d_dJdu, nullptr);
-  }
-  const BlksegShape s = blkseg_shape(c);
-  int r = ensure_lazy_bufs(c);
-  if (r) return r;
-  BlksegParams sp;
-  if ((r = blkseg_params(c, s, sp))) return r;
-  sp.u = d_u;
-  sp.u_copy = d_u != c->d_u ? c->d_u : nullptr;
-  sp.u_copy2 = c->d_u_lam;  // the co-states' rebuild (blku_costates) reads this copy and d_coef_lam
-  sp.J2 = d_J && d_J != c->d_J ? d_J : nullptr;
-  sp.coef2 = c->d_coef_lam;
-  sp.dJdu = d_dJdu;
-  const int mk = mark_begin(c, 2);
-  const hipError_t e = blkseg_launch<BLKSEG_FUSED>(c, order, s, sp);
-  mark_end(c, mk);
-  if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "k_blkseg_eval launch: %s", hipGetErrorString(e));
-  c->fwd_captured = false;
-  c->L_is_mu = false;
-  c->X_lazy = true;
-  c->L_lazy = true;
-  c->best_ready = true;
-  c->last_eval_mode = 6;
-  return QOC_OK;
-}
-
-// propagate on the segmented eval (the reference's f, examples/ipopt_callbacks_exp.jl:11-19): J, the λ_N coefficients
-// and G at every segment's end, x_k rebuilt on demand.  Applies where the fused eval does (any order: the forward half
-// has none) unless QOC_BLKSEG_SPLIT=0.
-bool blkseg_split_ok(const qoc_ctx* c) {
-  const char* env = getenv("QOC_BLKSEG_SPLIT");
-  if (env && !std::strcmp(env, "0")) return false;
-  return blkseg_ok(c, 3);
-}
-
-int blkseg_forward(qoc_ctx* c, const double* d_u, double* d_J) {
-  const BlksegShape s = blkseg_shape(c);
-  int r = ensure_lazy_bufs(c);
-  if (r) return r;
-  // G at every segment's end, and behind it D when the eval is penalised
-  const size_t gcount = (size_t)c->B * s.S * c->nblk * c->blk_nb * c->blk_nb;
-  const size_t gbytes = (blkseg_pen(c) ? 2 : 1) * gcount * sizeof(double2);
-  if (c->gseg_bytes < gbytes) {  // a new block layout (qoc_set_generators) or a penalty may need more
-    if (c->d_gseg) {
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      HIPCHK(c, hipFree(c->d_gseg));
-      c->d_gseg = nullptr;
-      c->dev_bytes -= c->gseg_bytes;
-      c->gseg_bytes = 0;
-    }
-    HIPCHK(c, hipMalloc((void**)&c->d_gseg, gbytes));
-    c->gseg_bytes = gbytes;
-    c->dev_bytes += gbytes;
-  }
-  BlksegParams sp;
-  if ((r = blkseg_params(c, s, sp))) return r;
-  sp.u = d_u;
-  sp.u_copy = d_u != c->d_u ? c->d_u : nullptr;  // the backward half and the stale check read d_u
-  sp.J2 = d_J && d_J != c->d_J ? d_J : nullptr;
-  sp.gseg = c->d_gseg;  // (the co-states' rebuild source stays the last grape_sensitivity's: the backward writes it)
-  sp.dseg = c->d_gseg + gcount;
-  const int mk = mark_begin(c, 1);
-  const hipError_t e = blkseg_launch<BLKSEG_FWD>(c, 1, s, sp);
-  mark_end(c, mk);
-  if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "k_blkseg_eval (forward) launch: %s", hipGetErrorString(e));
-  c->fwd_captured = false;
-  c->X_lazy = true;
-  c->best_ready = true;
-  c->fwd_kind = 1;
-  c->props_since_reset++;
-  return QOC_OK;
-}
-
-// grape_sensitivity after blkseg_forward (the reference's f_grad, :21-31): phase 3 from the stored G; the co-states are
-// rebuilt on demand from the forward's copies of u and the λ_N coefficients
-int blkseg_backward(qoc_ctx* c, int order, double* d_dJdu, const int* stale) {
-  const BlksegShape s = blkseg_shape(c);
-  BlksegParams sp;
-  int r = blkseg_params(c, s, sp);
-  if (r) return r;
-  if ((r = ensure_lazy_bufs(c))) return r;
-  sp.u = c->d_u;
-  sp.u_copy2 = c->d_u_lam;  // λ_k rebuilt on demand from this u and the forward's λ_N coefficients
-  sp.coef2 = c->d_coef_lam;
-  sp.dJdu = d_dJdu;
-  sp.gseg = c->d_gseg;
-  sp.dseg = c->d_gseg + (size_t)c->B * s.S * c->nblk * c->blk_nb * c->blk_nb;
-  sp.stale = stale;
-  const int mk = mark_begin(c, 2);
-  const hipError_t e = blkseg_launch<BLKSEG_BWD>(c, order, s, sp);
-  mark_end(c, mk);
-  if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "k_blkseg_eval (backward) launch: %s", hipGetErrorString(e));
-  c->L_is_mu = false;
-  c->L_lazy = true;
-  c->last_eval_mode = 6;
   return QOC_OK;
 }
 

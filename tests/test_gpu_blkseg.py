@@ -9,78 +9,14 @@ import numpy as np
 import pytest
 
 import qoc_oracle as O
+from blkseg_util import assert_seed as _assert_seed, block_problem as _block_problem, case
+from blkseg_util import engine as _engine, eval_dev as _eval_dev
 
 pytestmark = pytest.mark.gpu
 
 
-def _engine(prob, B, monkeypatch, seg="1", S=None, W=None):
-    from qoc_amd import GrapeEngine
-    monkeypatch.setenv("QOC_BLOCKS", "1")
-    monkeypatch.setenv("QOC_BLKU", "1")
-    monkeypatch.setenv("QOC_BLKSEG", seg)
-    for k, v in (("QOC_BLKSEG_S", S), ("QOC_BLKSEG_W", W)):
-        if v is None:
-            monkeypatch.delenv(k, raising=False)
-        else:
-            monkeypatch.setenv(k, str(v))
-    e = GrapeEngine(prob.A0, prob.A, prob.x0, prob.Nt, B=B)
-    e.set_cost_trace(prob.x_target, prob.n)
-    e.set_chain("taylor")
-    return e
-
-
-def _eval_dev(e, u, order=3):
-    import torch
-    B, nu, Nt = u.shape
-    ud = torch.from_numpy(np.ascontiguousarray(np.transpose(u, (0, 2, 1)))).cuda()
-    Jd = torch.empty(B, dtype=torch.float64, device="cuda")
-    gd = torch.empty(B, Nt, nu, dtype=torch.float64, device="cuda")
-    e.eval_device(ud.data_ptr(), order, Jd.data_ptr(), gd.data_ptr())
-    e.synchronize()
-    return Jd.cpu().numpy(), np.transpose(gd.cpu().numpy(), (0, 2, 1))
-
-
-def _assert_seed(J, g, Jr, gr, tag):
-    assert abs(J - Jr) <= 1e-12, (tag, J - Jr)
-    rel = np.linalg.norm(g - gr) / np.linalg.norm(gr)
-    assert rel <= 1e-10, (tag, rel)
-
-
 def _cases():
-    from qoc_amd import systems
-    out = {}
-    p = systems.zz_problem(60, tgate=6.0)  # N = 9, 3 blocks of 3, m = 4, nu = 2
-    out["zz"] = (p, systems.zz_controls(3, 60, 6.0, seed=81))
-    p = systems.cavity_problem(N_cavity=10, Nt=50)  # N = 20, 10 blocks of 2, m = 2
-    out["cavity20"] = (p, systems.cavity_controls(3, p.Nt, seed=82))
-    p = systems.cavity_problem(N_cavity=20, Nt=77)  # N = 40 (the BASELINE system), 20 blocks of 2
-    out["cavity40"] = (p, systems.cavity_controls(2, p.Nt, seed=83))
-    return out
-
-
-def _block_problem(NB, nblk, nu, m, Nt, seed):
-    """Random skew-Hermitian generators (exactly: -i H dt with H = (G + G^H) / 2) with nblk blocks of NB rows under a
-    random permutation, the last block one row short (padding)."""
-    from qoc_amd import systems
-    rng = np.random.default_rng(seed)
-    sizes = [NB] * (nblk - 1) + [NB - 1]
-    N = sum(sizes)
-    perm = rng.permutation(N)
-    gens = []
-    for j in range(nu + 1):
-        H = np.zeros((N, N), complex)
-        o = 0
-        for s in sizes:
-            G = rng.standard_normal((s, s)) + 1j * rng.standard_normal((s, s))
-            H[o:o + s, o:o + s] = (G + G.conj().T) / 2
-            o += s
-        H = H[np.ix_(perm, perm)]
-        gens.append(-1j * H * (0.08 if j == 0 else 0.05))
-    x0 = np.linalg.qr(rng.standard_normal((N, m)) + 1j * rng.standard_normal((N, m)))[0]
-    xt = np.linalg.qr(rng.standard_normal((N, m)) + 1j * rng.standard_normal((N, m)))[0]
-    prob = systems.Problem("blocks", gens[0], gens[1:], x0, xt, float(m), Nt, "fp64")
-    u = rng.uniform(-1, 1, size=(2, nu, Nt))
-    return prob, u
+    return {name: case(name)[:2] for name in ("zz", "cavity20", "cavity40")}
 
 
 @pytest.mark.parametrize("name", ["zz", "cavity20", "cavity40"])
@@ -152,7 +88,7 @@ def test_segmented_gradient_orders(built_lib, monkeypatch, name, order):
 def test_segmented_random_permuted_blocks(built_lib, monkeypatch, NB, nblk, nu, m):
     """Random permuted blocks of 2 / 3 rows (a short last block: padding rows), one or two controls, 1..8 columns,
     24 blocks (two segments per wave)."""
-    prob, u = _block_problem(NB, nblk, nu, m, Nt=45, seed=NB * 100 + nblk + nu + m)
+    prob, u, _ = _block_problem(NB, nblk, nu, m, Nt=45, seed=NB * 100 + nblk + nu + m)
     e = _engine(prob, 2, monkeypatch)
     J, g = _eval_dev(e, u)
     assert e.info()["backward"] == "segmented", e.info()

@@ -10,7 +10,7 @@ trajectory's largest entry.  The oracle's own exact gradient lies 7e-6 (zz) to 4
 these cases, so an eval that ran order 3 under the exact tag would miss the bar by five orders.
 
 The recipes (_engine, _eval_dev, _split_dev, _block_problem, the shipped cases and their penalties) are those of
-tests/test_gpu_blkseg.py and tests/test_gpu_blkseg_penalty.py.
+tests/blkseg_util.py.
 """
 import functools
 
@@ -18,87 +18,20 @@ import numpy as np
 import pytest
 
 import qoc_oracle as O
+from blkseg_util import MU, assert_seed as _assert_seed, block_problem as _block_problem, case as _case
+from blkseg_util import bufs as _bufs, dev as _dev, engine as _engine, eval_dev, pen as _pen, split_dev
 
 pytestmark = pytest.mark.gpu
 
-MU = 0.37
 EX = "exact"
 
 
-def _engine(prob, B, monkeypatch, pen=None, seg="1", S=None, W=None, segex=None):
-    from qoc_amd import GrapeEngine
-    monkeypatch.setenv("QOC_BLOCKS", "1")
-    monkeypatch.setenv("QOC_BLKU", "1")
-    monkeypatch.setenv("QOC_BLKSEG", seg)
-    monkeypatch.delenv("QOC_BLKSEG_PEN", raising=False)
-    for k, v in (("QOC_BLKSEG_S", S), ("QOC_BLKSEG_W", W), ("QOC_BLKSEG_EXACT", segex)):
-        if v is None:
-            monkeypatch.delenv(k, raising=False)
-        else:
-            monkeypatch.setenv(k, str(v))
-    e = GrapeEngine(prob.A0, prob.A, prob.x0, prob.Nt, B=B)
-    e.set_cost_trace(prob.x_target, prob.n)
-    e.set_chain("taylor")
-    if pen is not None:
-        e.set_state_penalty(*pen)
-    return e
-
-
-def _dev(u):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(np.transpose(u, (0, 2, 1)))).cuda()
-
-
-def _bufs(B, Nt, nu):
-    import torch
-    return (torch.full((B,), np.nan, dtype=torch.float64, device="cuda"),
-            torch.full((B, Nt, nu), np.nan, dtype=torch.float64, device="cuda"))
-
-
 def _eval_dev(e, u, order=EX):
-    B, nu, Nt = u.shape
-    ud = _dev(u)
-    Jd, gd = _bufs(B, Nt, nu)
-    e.eval_device(ud.data_ptr(), order, Jd.data_ptr(), gd.data_ptr())
-    e.synchronize()
-    return Jd.cpu().numpy(), np.transpose(gd.cpu().numpy(), (0, 2, 1))
+    return eval_dev(e, u, order)
 
 
 def _split_dev(e, u, order=EX, check=None):
-    B, nu, Nt = u.shape
-    ud = _dev(u)
-    Jd, gd = _bufs(B, Nt, nu)
-    e.propagate_device(ud.data_ptr(), Jd.data_ptr())
-    if check is not None:
-        check(e.info())
-    e.grape_sensitivity_device(ud.data_ptr(), order, gd.data_ptr())
-    e.synchronize()
-    return Jd.cpu().numpy(), np.transpose(gd.cpu().numpy(), (0, 2, 1))
-
-
-def _assert_seed(J, g, Jr, gr, tag):
-    rel = np.linalg.norm(g - gr) / np.linalg.norm(gr)
-    print(tag, "dJ", J - Jr, "rel dJdu", rel)
-    assert abs(J - Jr) <= 1e-12, (tag, J - Jr)
-    assert rel <= 1e-10, (tag, rel)
-
-
-def _pen(pen):
-    return [int(r) for r in pen[0]], [int(c) for c in pen[1]], float(pen[2])
-
-
-@functools.lru_cache(maxsize=None)
-def _case(name):
-    """(problem, controls, penalty) of the shipped systems (tests/test_gpu_blkseg.py, test_gpu_blkseg_penalty.py)."""
-    from qoc_amd import systems
-    if name == "zz":  # N = 9, 3 blocks of 3, m = 4, nu = 2; the reference's guard states |20>, |21>, |22>
-        p = systems.zz_problem(60, tgate=6.0)
-        qb = systems.QuantumBasis([3, 3])
-        return p, systems.zz_controls(3, 60, 6.0, seed=81), (tuple(qb(["20", "21", "22"])), (0, 1, 2, 3), MU)
-    if name == "cavity20":  # N = 20, 10 blocks of 2, m = 2
-        p = systems.cavity_problem(N_cavity=10, Nt=50)
-        return p, systems.cavity_controls(3, p.Nt, seed=82), ((16, 17, 18, 19, 5), (0, 1), MU)
-    raise KeyError(name)
+    return split_dev(e, u, order, check)
 
 
 @functools.lru_cache(maxsize=None)
@@ -107,31 +40,6 @@ def _oracle(name, order=EX, pen=False):
     prob, u, p = _case(name)
     return tuple(O.grape_eval(prob.A0, prob.A, u[b], prob.x0, prob.x_target, prob.n, order=order,
                               penalty=_pen(p) if pen else None) for b in range(u.shape[0]))
-
-
-def _block_problem(NB, nblk, nu, m, Nt, seed, scale=1.0):
-    """Random skew-Hermitian generators (exactly: -i H dt with H = (G + G^H) / 2) with nblk blocks of NB rows under a
-    random permutation, the last block one row short (padding); scale raises every generator."""
-    from qoc_amd import systems
-    rng = np.random.default_rng(seed)
-    sizes = [NB] * (nblk - 1) + [NB - 1]
-    N = sum(sizes)
-    perm = rng.permutation(N)
-    gens = []
-    for j in range(nu + 1):
-        H = np.zeros((N, N), complex)
-        o = 0
-        for s in sizes:
-            G = rng.standard_normal((s, s)) + 1j * rng.standard_normal((s, s))
-            H[o:o + s, o:o + s] = (G + G.conj().T) / 2
-            o += s
-        H = H[np.ix_(perm, perm)]
-        gens.append(-1j * H * (0.08 if j == 0 else 0.05) * scale)
-    x0 = np.linalg.qr(rng.standard_normal((N, m)) + 1j * rng.standard_normal((N, m)))[0]
-    xt = np.linalg.qr(rng.standard_normal((N, m)) + 1j * rng.standard_normal((N, m)))[0]
-    prob = systems.Problem("blocks", gens[0], gens[1:], x0, xt, float(m), Nt, "fp64")
-    u = rng.uniform(-1, 1, size=(2, nu, Nt))
-    return prob, u
 
 
 def _theta(P):
@@ -227,7 +135,7 @@ def test_exact_series_degree_classes_and_halving(built_lib, monkeypatch, amp):
 def test_exact_random_permuted_blocks(built_lib, monkeypatch, NB, nblk, nu, m, scale):
     """Random permuted blocks of 2 / 3 rows (padding rows, one control, two segments per wave); the last case raises
     the generators so that blocks of 3 rows run with halvings (J > 0: ρ beyond θ_17, checked here on the CPU)."""
-    prob, u = _block_problem(NB, nblk, nu, m, Nt=45, seed=NB * 100 + nblk + nu + m, scale=scale)
+    prob, u, _ = _block_problem(NB, nblk, nu, m, Nt=45, seed=NB * 100 + nblk + nu + m, scale=scale)
     if scale != 1.0:
         assert _rho_lower(prob, u) > _theta(17)
     e = _engine(prob, 2, monkeypatch)

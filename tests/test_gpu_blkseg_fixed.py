@@ -1,4 +1,4 @@
-"""The fixed costs around the segmented block eval's two loops (csrc/qoc_blkseg.hpp, csrc/qoc_run_blk.hip): the
+"""The fixed costs around the segmented block eval's two loops (csrc/qoc_blkseg.hpp, csrc/qoc_run_blkseg.hip): the
 packed table of generator blocks that the host builds with the block layout and the prologue copies (it has to follow
 qoc_set_generators), X_target staged in LDS for the cost section, the launch shape and the kernels' dynamic-LDS limit
 kept in the context between evals, and the fence-free phase events.  Conventions and bars of
@@ -11,74 +11,16 @@ import numpy as np
 import pytest
 
 import qoc_oracle as O
+from blkseg_util import assert_seed as _assert_seed, block_problem as _block_problem
+from blkseg_util import engine as _engine, eval_dev as _eval_dev
 
 pytestmark = pytest.mark.gpu
-
-
-def _engine(prob, B, monkeypatch, S=None):
-    from qoc_amd import GrapeEngine
-    monkeypatch.setenv("QOC_BLOCKS", "1")
-    monkeypatch.setenv("QOC_BLKU", "1")
-    monkeypatch.setenv("QOC_BLKSEG", "1")
-    monkeypatch.delenv("QOC_BLKSEG_W", raising=False)
-    for k, v in (("QOC_BLKSEG_S", S),):
-        if v is None:
-            monkeypatch.delenv(k, raising=False)
-        else:
-            monkeypatch.setenv(k, str(v))
-    e = GrapeEngine(prob.A0, prob.A, prob.x0, prob.Nt, B=B)
-    e.set_cost_trace(prob.x_target, prob.n)
-    e.set_chain("taylor")
-    return e
-
-
-def _eval_dev(e, u, order=3):
-    import torch
-    B, nu, Nt = u.shape
-    ud = torch.from_numpy(np.ascontiguousarray(np.transpose(u, (0, 2, 1)))).cuda()
-    Jd = torch.empty(B, dtype=torch.float64, device="cuda")
-    gd = torch.empty(B, Nt, nu, dtype=torch.float64, device="cuda")
-    e.eval_device(ud.data_ptr(), order, Jd.data_ptr(), gd.data_ptr())
-    e.synchronize()
-    return Jd.cpu().numpy(), np.transpose(gd.cpu().numpy(), (0, 2, 1))
-
-
-def _assert_seed(J, g, Jr, gr, tag):
-    print(tag, "dJ", abs(J - Jr), "rel", np.linalg.norm(g - gr) / np.linalg.norm(gr))
-    assert abs(J - Jr) <= 1e-12, (tag, J - Jr)
-    rel = np.linalg.norm(g - gr) / np.linalg.norm(gr)
-    assert rel <= 1e-10, (tag, rel)
 
 
 def _assert_oracle(prob, u, J, g, tag):
     for b in range(u.shape[0]):
         J0, g0, _ = O.grape_eval(prob.A0, prob.A, u[b], prob.x0, prob.x_target, prob.n, order=3)
         _assert_seed(J[b], g[b], J0, g0, (tag, b))
-
-
-def _block_problem(NB, nblk, nu, m, Nt, seed):
-    """Random exactly skew-Hermitian generators with nblk blocks of NB rows under a random permutation, the last block
-    one row short (a padded row), as in tests/test_gpu_blkseg.py."""
-    from qoc_amd import systems
-    rng = np.random.default_rng(seed)
-    sizes = [NB] * (nblk - 1) + [NB - 1]
-    N = sum(sizes)
-    perm = rng.permutation(N)
-    gens = []
-    for j in range(nu + 1):
-        H = np.zeros((N, N), complex)
-        o = 0
-        for s in sizes:
-            G = rng.standard_normal((s, s)) + 1j * rng.standard_normal((s, s))
-            H[o:o + s, o:o + s] = (G + G.conj().T) / 2
-            o += s
-        H = H[np.ix_(perm, perm)]
-        gens.append(-1j * H * (0.08 if j == 0 else 0.05))
-    x0 = np.linalg.qr(rng.standard_normal((N, m)) + 1j * rng.standard_normal((N, m)))[0]
-    xt = np.linalg.qr(rng.standard_normal((N, m)) + 1j * rng.standard_normal((N, m)))[0]
-    prob = systems.Problem("blocks", gens[0], gens[1:], x0, xt, float(m), Nt, "fp64")
-    u = rng.uniform(-1, 1, size=(2, nu, Nt))
-    return prob, u
 
 
 def _cavity20():
@@ -89,8 +31,8 @@ def _cavity20():
 
 def _setter_cases():
     out = {"cavity20": _cavity20()}
-    out["blocks2"] = _block_problem(2, 7, 1, 3, Nt=45, seed=711)
-    out["blocks3"] = _block_problem(3, 5, 2, 2, Nt=45, seed=712)
+    out["blocks2"] = _block_problem(2, 7, 1, 3, Nt=45, seed=711)[:2]
+    out["blocks3"] = _block_problem(3, 5, 2, 2, Nt=45, seed=712)[:2]
     return out
 
 
@@ -263,7 +205,7 @@ def test_launch_shape_kept_between_evals_follows_its_inputs(built_lib, monkeypat
     for b in range(B):
         _assert_seed(J7[b], g7[b], J[b], g[b], ("S=7", b))
     _assert_oracle(prob, u, J, g, "S default")
-    pb, _ = _block_problem(3, 7, 2, 2, Nt=prob.Nt, seed=714)
+    pb, _, _ = _block_problem(3, 7, 2, 2, Nt=prob.Nt, seed=714)
     assert pb.N == prob.N
     p2 = dataclasses.replace(prob, A0=pb.A0, A=pb.A)
     e.set_generators(p2.A0, p2.A)

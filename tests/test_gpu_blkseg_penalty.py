@@ -13,86 +13,11 @@ import numpy as np
 import pytest
 
 import qoc_oracle as O
+from blkseg_util import MU, assert_seed as _assert_seed, block_problem as _block_problem, case as _case
+from blkseg_util import bufs as _bufs, dev as _dev, engine as _engine, eval_dev as _eval_dev, pen as _pen
+from blkseg_util import split_dev as _split_dev
 
 pytestmark = pytest.mark.gpu
-
-MU = 0.37
-
-
-def _engine(prob, B, monkeypatch, pen=None, seg="1", S=None, W=None, segpen=None):
-    from qoc_amd import GrapeEngine
-    monkeypatch.setenv("QOC_BLOCKS", "1")
-    monkeypatch.setenv("QOC_BLKU", "1")
-    monkeypatch.setenv("QOC_BLKSEG", seg)
-    for k, v in (("QOC_BLKSEG_S", S), ("QOC_BLKSEG_W", W), ("QOC_BLKSEG_PEN", segpen)):
-        if v is None:
-            monkeypatch.delenv(k, raising=False)
-        else:
-            monkeypatch.setenv(k, str(v))
-    e = GrapeEngine(prob.A0, prob.A, prob.x0, prob.Nt, B=B)
-    e.set_cost_trace(prob.x_target, prob.n)
-    e.set_chain("taylor")
-    if pen is not None:
-        e.set_state_penalty(*pen)
-    return e
-
-
-def _dev(u):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(np.transpose(u, (0, 2, 1)))).cuda()
-
-
-def _bufs(B, Nt, nu):
-    import torch
-    return (torch.full((B,), np.nan, dtype=torch.float64, device="cuda"),
-            torch.full((B, Nt, nu), np.nan, dtype=torch.float64, device="cuda"))
-
-
-def _eval_dev(e, u, order=3):
-    B, nu, Nt = u.shape
-    ud = _dev(u)
-    Jd, gd = _bufs(B, Nt, nu)
-    e.eval_device(ud.data_ptr(), order, Jd.data_ptr(), gd.data_ptr())
-    e.synchronize()
-    return Jd.cpu().numpy(), np.transpose(gd.cpu().numpy(), (0, 2, 1))
-
-
-def _split_dev(e, u, order=3):
-    B, nu, Nt = u.shape
-    ud = _dev(u)
-    Jd, gd = _bufs(B, Nt, nu)
-    e.propagate_device(ud.data_ptr(), Jd.data_ptr())
-    e.grape_sensitivity_device(ud.data_ptr(), order, gd.data_ptr())
-    e.synchronize()
-    return Jd.cpu().numpy(), np.transpose(gd.cpu().numpy(), (0, 2, 1))
-
-
-def _assert_seed(J, g, Jr, gr, tag):
-    print(tag, "dJ", J - Jr, "rel dJdu", np.linalg.norm(g - gr) / np.linalg.norm(gr))
-    assert abs(J - Jr) <= 1e-12, (tag, J - Jr)
-    rel = np.linalg.norm(g - gr) / np.linalg.norm(gr)
-    assert rel <= 1e-10, (tag, rel)
-
-
-@functools.lru_cache(maxsize=None)
-def _case(name):
-    """(problem, controls, penalty) of the shipped systems."""
-    from qoc_amd import systems
-    if name == "zz":  # N = 9, 3 blocks of 3, m = 4, nu = 2; the reference's guard states |20>, |21>, |22>
-        p = systems.zz_problem(60, tgate=6.0)
-        qb = systems.QuantumBasis([3, 3])
-        return p, systems.zz_controls(3, 60, 6.0, seed=81), (tuple(qb(["20", "21", "22"])), (0, 1, 2, 3), MU)
-    if name == "cavity20":  # N = 20, 10 blocks of 2, m = 2
-        p = systems.cavity_problem(N_cavity=10, Nt=50)
-        return p, systems.cavity_controls(3, p.Nt, seed=82), ((16, 17, 18, 19, 5), (0, 1), MU)
-    if name == "cavity40":  # N = 40 (the BASELINE system), 20 blocks of 2: the top two cavity levels of both qubit states
-        p = systems.cavity_problem(N_cavity=20, Nt=77)
-        return p, systems.cavity_controls(2, p.Nt, seed=83), ((18, 19, 38, 39), (0, 1), MU)
-    raise KeyError(name)
-
-
-def _pen(pen):
-    return [int(r) for r in pen[0]], [int(c) for c in pen[1]], float(pen[2])
 
 
 @functools.lru_cache(maxsize=None)
@@ -101,37 +26,6 @@ def _oracle(name, order=3):
     prob, u, pen = _case(name)
     return tuple(O.grape_eval(prob.A0, prob.A, u[b], prob.x0, prob.x_target, prob.n, order=order, penalty=_pen(pen))
                  for b in range(u.shape[0]))
-
-
-def _block_problem(NB, nblk, nu, m, Nt, seed):
-    """Random skew-Hermitian generators (exactly: -i H dt with H = (G + G^H) / 2) with nblk blocks of NB rows under a
-    random permutation, the last block one row short (padding): the recipe of tests/test_gpu_blkseg.py, which also
-    returns each block's rows in the permuted order."""
-    from qoc_amd import systems
-    rng = np.random.default_rng(seed)
-    sizes = [NB] * (nblk - 1) + [NB - 1]
-    N = sum(sizes)
-    perm = rng.permutation(N)
-    gens = []
-    for j in range(nu + 1):
-        H = np.zeros((N, N), complex)
-        o = 0
-        for s in sizes:
-            G = rng.standard_normal((s, s)) + 1j * rng.standard_normal((s, s))
-            H[o:o + s, o:o + s] = (G + G.conj().T) / 2
-            o += s
-        H = H[np.ix_(perm, perm)]
-        gens.append(-1j * H * (0.08 if j == 0 else 0.05))
-    x0 = np.linalg.qr(rng.standard_normal((N, m)) + 1j * rng.standard_normal((N, m)))[0]
-    xt = np.linalg.qr(rng.standard_normal((N, m)) + 1j * rng.standard_normal((N, m)))[0]
-    prob = systems.Problem("blocks", gens[0], gens[1:], x0, xt, float(m), Nt, "fp64")
-    u = rng.uniform(-1, 1, size=(2, nu, Nt))
-    inv = np.argsort(perm)  # row perm[i] of the block-ordered matrix sits at row i
-    blocks, o = [], 0
-    for s in sizes:
-        blocks.append(sorted(int(inv[r]) for r in range(o, o + s)))
-        o += s
-    return prob, u, blocks
 
 
 def _block_penalty(blocks, m):

@@ -11,70 +11,24 @@ import numpy as np
 import pytest
 
 import qoc_oracle as O
+from blkseg_util import MU, assert_seed as _assert_seed, engine as _engine, eval_dev, split_dev
 
 pytestmark = pytest.mark.gpu
 
-MU = 0.37
 PEN = ([16, 17, 18, 19, 5], [0, 1], MU)  # tests/test_gpu_blkseg_penalty.py, cavity20
 
 
-def _engine(prob, B, monkeypatch, S=None, pen=None):
-    from qoc_amd import GrapeEngine
-    monkeypatch.setenv("QOC_BLOCKS", "1")
-    monkeypatch.setenv("QOC_BLKU", "1")
-    monkeypatch.setenv("QOC_BLKSEG", "1")
-    for k in ("QOC_BLKSEG_W", "QOC_BLKSEG_PEN", "QOC_BLKSEG_EXACT", "QOC_BLKSEG_SPLIT"):
-        monkeypatch.delenv(k, raising=False)
-    if S is None:
-        monkeypatch.delenv("QOC_BLKSEG_S", raising=False)
-    else:
-        monkeypatch.setenv("QOC_BLKSEG_S", str(S))
-    e = GrapeEngine(prob.A0, prob.A, prob.x0, prob.Nt, B=B)
-    e.set_cost_trace(prob.x_target, prob.n)
-    e.set_chain("taylor")
-    if pen is not None:
-        e.set_state_penalty(*pen)
-    return e
-
-
-def _dev(u):
-    import torch
-    return torch.from_numpy(np.ascontiguousarray(np.transpose(u, (0, 2, 1)))).cuda()
-
-
-def _bufs(B, Nt, nu):
-    import torch
-    return (torch.full((B,), np.nan, dtype=torch.float64, device="cuda"),
-            torch.full((B, Nt, nu), np.nan, dtype=torch.float64, device="cuda"))
-
-
 def _eval_dev(e, u, order=3):
-    B, nu, Nt = u.shape
-    ud = _dev(u)
-    Jd, gd = _bufs(B, Nt, nu)
-    e.eval_device(ud.data_ptr(), order, Jd.data_ptr(), gd.data_ptr())
-    e.synchronize()
+    out = eval_dev(e, u, order)
     assert e.info()["backward"] == "segmented", e.info()
-    return Jd.cpu().numpy(), np.transpose(gd.cpu().numpy(), (0, 2, 1))
+    return out
 
 
 def _split_dev(e, u, order=3):
-    B, nu, Nt = u.shape
-    ud = _dev(u)
-    Jd, gd = _bufs(B, Nt, nu)
-    e.propagate_device(ud.data_ptr(), Jd.data_ptr())
-    e.grape_sensitivity_device(ud.data_ptr(), order, gd.data_ptr())
-    e.synchronize()
+    out = split_dev(e, u, order)
     info = e.info()
     assert info["split_forward"] == "segmented" and info["backward"] == "segmented", info
-    return Jd.cpu().numpy(), np.transpose(gd.cpu().numpy(), (0, 2, 1))
-
-
-def _assert_seed(J, g, Jr, gr, tag):
-    rel = np.linalg.norm(g - gr) / np.linalg.norm(gr)
-    print(tag, "dJ", J - Jr, "rel dJdu", rel)
-    assert abs(J - Jr) <= 1e-12, (tag, J - Jr)
-    assert rel <= 1e-10, (tag, rel)
+    return out
 
 
 @functools.lru_cache(maxsize=None)
