@@ -70,7 +70,10 @@ int qoc_set_cost(qoc_ctx* ctx, int kind, const double* X_target, double n);
 /* Guard-state penalty L = mu sum |x[P,C]|^2 (src/penalty_fcns.jl:1-11), summed over the Nt + 1 states in J and added
  * as 2 mu x_k[P,C] to every co-state; 0-based indices; mu = 0 (or an empty P or C) disables.  Generators with
  * invariant blocks of 2-3 rows keep the one-launch segmented eval and its split form with the penalty set
- * (QOC_BLKSEG_PEN=0: the block chains instead); a co-state source (qoc_set_costate_source) takes the chains.  May be
+ * (QOC_BLKSEG_PEN=0: the block chains instead); a co-state source (qoc_set_costate_source) takes the chains.
+ * Generators with invariant blocks of 5-16 rows keep the stored / interpolating block propagators (order 3, TRACE and
+ * ZCAL costs, both call forms): the forward chain adds the penalty's sum, the backward chain runs lambda_k with the
+ * sources (QOC_BLKP_PEN=0: the Chebyshev block chains instead); rows of a block that carries no state add nothing.  May be
  * called on a live context: lazily kept states / co-states are materialised first, and a propagate made before the
  * call is followed by a grape_sensitivity on rebuilt states. */
 int qoc_set_state_penalty(qoc_ctx* ctx, const int* P, int np, const int* C, int nc, double mu);
@@ -90,7 +93,9 @@ int qoc_grape_sensitivity(qoc_ctx* ctx, const double* u, int dUkdp_order,
  * src/gradient_computations.jl:47-49, 55-57): dLdx holds dL_dx(x_k) for every seed and k = 0..Nt
  * (B x (Nt+1) x N x m, the states' layout), added to λ_k by the following grape_sensitivity calls until cleared
  * with NULL.  The host evaluates the closure on the states (qoc_get_states); J's sum(L, x) stays with the
- * caller.  Not on the Tsit5 path (compute_pwc_gradient has no dL_dx). */
+ * caller.  Not on the Tsit5 path (compute_pwc_gradient has no dL_dx).  On blocks of 5-16 rows the stored block
+ * propagators' backward chain adds it (order 3, TRACE and ZCAL costs; QOC_BLKP_PEN=0: the Chebyshev block chains);
+ * every block then counts as live, since lambda_k is nonzero on rows that carry no state. */
 int qoc_set_costate_source(qoc_ctx* ctx, const double* dLdx);
 
 /* compress_states / decompress_states (src/utils.jl:96-109) inside the engine.  When the generators keep the

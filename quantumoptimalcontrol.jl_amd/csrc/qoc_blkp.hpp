@@ -25,6 +25,8 @@
 //   * k_blkp_ichain / k_blkp_ichain2 (one live wave block, one state column: the tunable bus, the default) let the chain
 //     waves form their own propagators in registers and apply them at once, nothing stored (k_blkp_phase precomputes
 //     the slices' e^{μ(u_k)}; the forward's cost is k_terminal_cost's).
+// A state penalty or a caller's co-state source (BlkpPen) runs on the same chains' PEN instantiations, the forward
+// chain first (it adds the penalty's sum to J), then the λ chain with the sources (it reads x_k), then k_blkp_grad on λ.
 #pragma once
 #include "qoc_blk.hpp"
 
@@ -740,6 +742,37 @@ __device__ __forceinline__ void blkp_dma(const void* src, unsigned lds) {
                : "memory");
 }
 
+// The state penalty (setup_state_penalty, src/penalty_fcns.jl:1-11) and the co-state sources (the reference's dL_dx
+// closure, src/gradient_computations.jl:47-49, 55-57) as the chains' PEN instantiations take them:
+//   J = Jfinal(x_N) + μ Σ_{k=0..Nt} Σ_{r in P, c in C} |x_k[r, c]|²,  λ_N = coef_c X_target + s_N,  λ_k = U_k^H λ_{k+1} + s_k,
+//   s_k = 2μ x_k on P x C + the caller's source of slice k (TChainArgs::src).
+// The masks as the segmented eval carries them: a 16-bit row mask per live wave block (bit i: row wrow[16 β + i] is in
+// P; a row of a dead block has no bit, its x_k is zero) and a 32-bit column mask.  The forward chains (FWD) add the
+// penalty sum, each owner lane over its own row slice by slice, then the wave's row, then the waves in order (no
+// atomics: the same u gives the same bits); the backward chains (PEN, !FWD) start from λ_N and add s_k to every step's
+// result before it goes to the exchange row, so they need x_k (TChainArgs::X) and run after the forward chain, and
+// they write λ_k itself where the unpenalised ones write μ_k.
+struct BlkpPen {
+  unsigned short prow[8];
+  unsigned pcol;
+};
+__device__ __forceinline__ double blkp_abs2(double2 v) { return fma(v.x, v.x, v.y * v.y); }
+// s_k of one state element: e its offset in a seed's (Nt + 1) N m states, pm: on P x C
+__device__ __forceinline__ double2 blkp_source(const double2* __restrict__ Xb, const double2* __restrict__ srcb, size_t e,
+                                               bool pm, bool act, double tmu) {
+  double2 s = make_double2(0.0, 0.0);
+  if (pm) {
+    const double2 x = Xb[e];
+    s = make_double2(tmu * x.x, tmu * x.y);
+  }
+  if (act && srcb) {
+    const double2 v = srcb[e];
+    s.x += v.x;
+    s.y += v.y;
+  }
+  return s;
+}
+
 // this lane's view of wave block β: row rb[i] (i = lane & 15), quarter q = lane >> 4, state column c
 struct BlkpLane {
   int i, q, beta, c, row;
@@ -766,10 +799,10 @@ __device__ __forceinline__ double2 blkp_dot4(const double (&ar)[4], const double
 
 // FWD: x_{k+1} = U_k x_k (lane (i, q) reads U_k[i][4q + t]); else μ_k = U_k^H μ_{k+1} (lane (i, q) reads
 // (U_k^H)[i][4q + t] = conj(U_k[4q + t][i])), μ_N = X_target (λ_k = coef ⊙ μ_k).  The forward ends with J and the λ_N
-// coefficients.
-template <bool FWD, int CH>
+// coefficients.  PEN (BlkpPen): the forward adds the penalty sum to J, the backward runs λ_k with the sources s_k.
+template <bool FWD, int CH, bool PEN = false>
 __device__ __forceinline__ void blkp_chain_body(const TChainArgs& g, const BlkArgs& bk, const double2* __restrict__ U,
-                                                const int b, const int useed0) {
+                                                const int b, const int useed0, const BlkpPen& pp = BlkpPen()) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   double* red = reinterpret_cast<double*>(smem);
   double* xN = red + 32;
@@ -793,9 +826,32 @@ __device__ __forceinline__ void blkp_chain_body(const TChainArgs& g, const BlkAr
     else v = ((const cx<double>*)g.Xt)[oe];
     v0 = make_double2(v.r, v.i);
   }
+  // PEN: this lane's element on P x C (all four lanes of a row: they all write the row's result to the exchange row)
+  const bool pm = PEN && act && ((pp.prow[ln.beta] >> ln.i) & 1) && ((pp.pcol >> ln.c) & 1);
+  const double tmu = 2.0 * g.mu;
+  const double2* const Xsb = reinterpret_cast<const double2*>((const cx<double>*)g.X + (size_t)b * (Nt + 1) * Nm);
+  const double2* const srcb =
+      PEN && !FWD && g.src ? reinterpret_cast<const double2*>((const cx<double>*)g.src + (size_t)b * (Nt + 1) * Nm) : nullptr;
+  double pen = 0.0;  // FWD: Σ_k |x_k|² of this owner lane's element
+  if constexpr (PEN && FWD) pen = pm && own ? blkp_abs2(v0) : 0.0;
+  if constexpr (PEN && !FWD) {  // λ_N = coef_c X_target + s_N
+    const cx<double> cf = g.coef[(size_t)b * 2 * m + ln.c];
+    const double2 s = blkp_source(Xsb, srcb, (size_t)Nt * Nm + oe, pm, act, tmu);
+    v0 = make_double2(cf.r * v0.x - cf.i * v0.y + s.x, cf.r * v0.y + cf.i * v0.x + s.y);
+  }
   xs[ln.i] = v0;
   __syncthreads();
   *(own ? Sb + (FWD ? 0 : (size_t)Nt * Nm) + oe : sink2) = v0;
+  // the owner lanes' sources of chunk cc's slices (clamped at the chain's end: those steps do not run)
+  auto sources = [&](int cc, double2 (&s)[CH]) __attribute__((always_inline)) {
+#pragma unroll
+    for (int jj = 0; jj < CH; ++jj)
+      s[jj] = blkp_source(Xsb, srcb, (size_t)max(Nt - 1 - (cc * CH + jj), 0) * Nm + oe, pm && own, own, tmu);
+  };
+  // PEN backward: the next chunk's s_k, loaded a chunk ahead beside the DMA (the chunk-start wait finds them a chunk
+  // old); at chunk start they go to the state rows Os, where each step reads its row before it writes its result there
+  double2 sn[CH];
+  if constexpr (PEN && !FWD) sources(0, sn);
   double xr[4], xi[4];
 #pragma unroll
   for (int t = 0; t < 4; ++t) {
@@ -846,6 +902,12 @@ __device__ __forceinline__ void blkp_chain_body(const TChainArgs& g, const BlkAr
     blkp_wave_sync();
     issue(c + 1);
     if (c > 0) flush(c - 1);
+    if constexpr (PEN && !FWD) {
+#pragma unroll
+      for (int jj = 0; jj < CH; ++jj)
+        if (ln.q == 0) Os[jj * 16 + ln.i] = sn[jj];
+      sources(c + 1, sn);
+    }
     blkp_wave_sync();
     const double2* const Us = Ub2 + (c & 1) * CH * 256;
     double ur[4], ui[4];  // slice jj's propagator quarter, read one slice ahead (off the chain's critical path)
@@ -857,6 +919,8 @@ __device__ __forceinline__ void blkp_chain_body(const TChainArgs& g, const BlkAr
     }
     for (int jj = 0; jj < CH; ++jj) {
       if (j0 + jj >= Nt) break;
+      double2 sv = make_double2(0.0, 0.0);
+      if constexpr (PEN && !FWD) sv = Os[jj * 16 + ln.i];  // s_k of this row
       double2 y = blkp_dot4(ur, ui, xr, xi);
       const int jn = min(jj + 1, CH - 1);
 #pragma unroll
@@ -866,6 +930,11 @@ __device__ __forceinline__ void blkp_chain_body(const TChainArgs& g, const BlkAr
         ui[t] = FWD ? pv.y : -pv.y;
       }
       y = xsum_rows2(y);
+      if constexpr (PEN && FWD) pen += pm && own ? blkp_abs2(y) : 0.0;
+      if constexpr (PEN && !FWD) {
+        y.x += sv.x;
+        y.y += sv.y;
+      }
       xs[ln.i] = y;
       blkp_wave_sync();
 #pragma unroll
@@ -887,9 +956,18 @@ __device__ __forceinline__ void blkp_chain_body(const TChainArgs& g, const BlkAr
       xN[2 * oe] = v.x;
       xN[2 * oe + 1] = v.y;
     }
+    double psum = 0.0;
+    if constexpr (PEN) {  // the owner lanes are the wave's first row of 16; the waves' sums in red[16 + w]
+      const double rs = row_sum16(pen);
+      if (l == 0) red[16 + (tid >> 6)] = rs;
+    }
     __syncthreads();
+    if constexpr (PEN) {
+      for (int w = 0; w < (nthr >> 6); ++w) psum += red[16 + w];
+      psum *= g.mu;
+    }
     chain_costs<double>(N, m, (const cx<double>*)g.Xt, [&](int o) { return cx<double>{xN[2 * o], xN[2 * o + 1]}; },
-                        g.cost_kind, g.n_norm, 0.0, red, g.J + b, g.coef + (size_t)b * 2 * m, g.sc);
+                        g.cost_kind, g.n_norm, psum, red, g.J + b, g.coef + (size_t)b * 2 * m, g.sc);
   }
 }
 
@@ -913,11 +991,11 @@ __global__ __launch_bounds__(512) void k_blkp_dual(const TChainArgs gf, const TC
 // one direction alone (the reference's split call form: the forward chain in propagate, the μ recurrence in
 // grape_sensitivity), one workgroup per seed seed0 + blockIdx.x; stale: a stale-u flag queued before the launch
 // (nonzero: nothing is written)
-template <bool FWD, int CH>
+template <bool FWD, int CH, bool PEN = false>
 __global__ __launch_bounds__(512) void k_blkp_chain(const TChainArgs g, const BlkArgs bk, const double2* __restrict__ U,
-                                                    int seed0, int useed0, const int* stale) {
+                                                    int seed0, int useed0, const int* stale, const BlkpPen pp) {
   if (stale && *stale != 0) return;
-  blkp_chain_body<FWD, CH>(g, bk, U, seed0 + (int)blockIdx.x, useed0);
+  blkp_chain_body<FWD, CH, PEN>(g, bk, U, seed0 + (int)blockIdx.x, useed0, pp);
 }
 
 // ---- one control, fused: the chains interpolate their own propagators (k_blkp_ichain) ----
@@ -1013,7 +1091,8 @@ struct BlkpIAcc {
 
 constexpr int BLKP_ISLB = 2;  // SYM: slices per pass through the entry slab (its LDS: BLKP_ISLB x 128 double2 per wave)
 // One chain wave's view of its (seed, direction): state rows, output and sink pointers, this lane's entries
-template <bool FWD, int SL, bool SYM>
+// PEN (BlkpPen, setup_pen): the forward sums the penalty in `pen`, the backward runs λ_k with the sources s_k
+template <bool FWD, int SL, bool SYM, bool PEN = false>
 struct BlkpIChain {
   static constexpr int NE = SYM ? 2 : 4;
   static constexpr int SLB = SL < BLKP_ISLB ? SL : BLKP_ISLB;  // SYM: slices per pass through the entry slab
@@ -1025,6 +1104,24 @@ struct BlkpIChain {
   const double2* phb;
   int off[NE];  // this lane's entries in a coefficient matrix
   int ks[4];    // SYM: the packed slots of this lane's four entries (i, 4q + t), -1: a padding row or column
+  // PEN: this lane's element on P x C, 2μ, the seed's x_k and the caller's sources, the owner lane's Σ_k |x_k|²
+  bool pm;
+  double tmu, pen;
+  const double2 *Xsb, *srcb;
+  __device__ __forceinline__ void setup_pen(const TChainArgs& g, const BlkpPen& pp, int b) {
+    pm = PEN && act && ((pp.prow[0] >> i) & 1) && (pp.pcol & 1);  // wave block 0, state column 0
+    tmu = 2.0 * g.mu;
+    pen = 0.0;
+    Xsb = reinterpret_cast<const double2*>((const cx<double>*)g.X + (size_t)b * (Nt + 1) * Nm);
+    srcb = PEN && !FWD && g.src ? reinterpret_cast<const double2*>((const cx<double>*)g.src + (size_t)b * (Nt + 1) * Nm)
+                                : nullptr;
+  }
+  // PEN backward: s_k of slices j0 .. j0 + SL - 1 (clamped at the chain's end: those steps do not run), read by all
+  // four lanes of a row; loaded before the chunk's interpolation, used after it
+  __device__ __forceinline__ void sources(int j0, double2 (&s)[SL]) const {
+#pragma unroll
+    for (int t = 0; t < SL; ++t) s[t] = blkp_source(Xsb, srcb, (size_t)max(Nt - 1 - j0 - t, 0) * Nm + oe, pm, act, tmu);
+  }
   __device__ __forceinline__ void setup(const TChainArgs& g, const BlkArgs& bk, const BlkpIntArgs& ia, int b) {
     Nt = g.Nt;
     l = threadIdx.x & 63;
@@ -1055,6 +1152,12 @@ struct BlkpIChain {
       if (FWD) v = ((const cx<double>*)g.x0 + (g.x0_per_seed ? (size_t)b * Nm : 0))[oe];
       else v = ((const cx<double>*)g.Xt)[oe];
       v0 = make_double2(v.r, v.i);
+    }
+    if constexpr (PEN && FWD) pen += pm && own ? blkp_abs2(v0) : 0.0;
+    if constexpr (PEN && !FWD) {  // λ_N = coef X_target + s_N (one state column)
+      const cx<double> cf = g.coef[(size_t)b * 2 * g.m];
+      const double2 s = blkp_source(Xsb, srcb, (size_t)Nt * Nm + oe, pm, act, tmu);
+      v0 = make_double2(cf.r * v0.x - cf.i * v0.y + s.x, cf.r * v0.y + cf.i * v0.x + s.y);
     }
     xs[i] = v0;
     *(own ? Sb + (FWD ? 0 : (size_t)Nt * Nm) + oe : sink2) = v0;
@@ -1101,9 +1204,9 @@ struct BlkpIChain {
     }
   }
   // the chunk's chain steps from the state in the exchange row xs (blkp_chain_body's arithmetic); the new states to
-  // Os, the last one left in xs
+  // Os, the last one left in xs; PEN: sk the backward's sources of the chunk (sources)
   __device__ __forceinline__ void steps(const double (&ur)[SL][4], const double (&ui)[SL][4], double2* xs, double2* Os,
-                                        int j0) {
+                                        int j0, const double2 (&sk)[SL]) {
     double xr[4], xi[4];
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -1116,6 +1219,11 @@ struct BlkpIChain {
       if (j0 + s >= Nt) break;  // uniform
       double2 y = blkp_dot4(ur[s], ui[s], xr, xi);
       y = xsum_rows2(y);
+      if constexpr (PEN && FWD) pen += pm && own ? blkp_abs2(y) : 0.0;
+      if constexpr (PEN && !FWD) {
+        y.x += sk[s].x;
+        y.y += sk[s].y;
+      }
       blkp_wave_sync();  // every lane has read the row
       xs[i] = y;
       blkp_wave_sync();
@@ -1146,11 +1254,13 @@ struct BlkpIChain {
 };
 
 // one wave per (seed, direction): form, steps, flush, chunk after chunk
-template <bool FWD, int SL, bool SYM>
+// (PEN forward: the seed's penalty sum μ Σ goes to J[b], where k_terminal_cost takes it up)
+template <bool FWD, int SL, bool SYM, bool PEN>
 __device__ __forceinline__ void blkp_ichain_body(const TChainArgs& g, const BlkArgs& bk, const BlkpIntArgs& ia,
-                                                 const double2* Ms, double2* xs, const int b) {
-  BlkpIChain<FWD, SL, SYM> cw;
+                                                 const double2* Ms, double2* xs, const int b, const BlkpPen& pp) {
+  BlkpIChain<FWD, SL, SYM, PEN> cw;
   cw.setup(g, bk, ia, b);
+  if constexpr (PEN) cw.setup_pen(g, pp, b);
   double2* const Os = xs + 32;       // [s][i]: x_{k+1} / μ_k of row i
   double2* const Es = Os + SL * 16;  // SYM: [s][slot] the slices' packed entries
   double* const Ts = reinterpret_cast<double*>(Es + (SYM ? SL * 128 : 0));  // [i][s] the chunk's T_i(ξ_s)
@@ -1158,10 +1268,16 @@ __device__ __forceinline__ void blkp_ichain_body(const TChainArgs& g, const BlkA
   blkp_wave_sync();
   for (int j0 = 0; j0 < g.Nt; j0 += SL) {
     double ur[SL][4], ui[SL][4];
+    double2 sk[SL];
+    if constexpr (PEN && !FWD) cw.sources(j0, sk);
     cw.form(ia, Ms, Es, Ts, j0, ur, ui);
-    cw.steps(ur, ui, xs, Os, j0);
+    cw.steps(ur, ui, xs, Os, j0, sk);
     cw.flush(Os, j0);
     blkp_wave_sync();  // Os and Es are rewritten by the next chunk
+  }
+  if constexpr (PEN && FWD) {  // the owner lanes are the wave's first row of 16
+    const double rs = row_sum16(cw.pen);
+    if (cw.l == 0) g.J[b] = g.mu * rs;
   }
 }
 
@@ -1169,13 +1285,16 @@ __device__ __forceinline__ void blkp_ichain_body(const TChainArgs& g, const BlkA
 // chunks c = r, r + 2, ...; it forms chunk c's propagator entries, waits until its partner has run chunk c - 1 (the
 // pair's chunk counter in LDS), runs chunk c's steps from the state the partner left in the pair's exchange row at the
 // top issue priority, stores the chunk's states and publishes c + 1.  So one wave's latency-bound chain steps run while
-// the other forms the next chunk on the same SIMD.
-template <bool FWD, int SL, bool SYM>
+// the other forms the next chunk on the same SIMD.  PEN forward: each wave sums the penalty over its own chunks; role
+// 1 leaves its sum in the pair's LDS slot ps before it publishes its last chunk, role 0 adds it to its own (role 0
+// then role 1) and writes μ Σ to J[b].
+template <bool FWD, int SL, bool SYM, bool PEN>
 __device__ __forceinline__ void blkp_ichain_pair_body(const TChainArgs& g, const BlkArgs& bk, const BlkpIntArgs& ia,
-                                                      const double2* Ms, double2* xs, int* flag, double2* wl,
-                                                      const int role, const int b) {
-  BlkpIChain<FWD, SL, SYM> cw;
+                                                      const double2* Ms, double2* xs, int* flag, double* ps, double2* wl,
+                                                      const int role, const int b, const BlkpPen& pp) {
+  BlkpIChain<FWD, SL, SYM, PEN> cw;
   cw.setup(g, bk, ia, b);
+  if constexpr (PEN) cw.setup_pen(g, pp, b);
   double2* const Os = wl;            // this wave's [s][i]
   double2* const Es = Os + SL * 16;  // SYM: this wave's slab
   double* const Ts = reinterpret_cast<double*>(Es + (SYM ? BLKP_ISLB * 128 : 0));  // [i][s] the chunk's T_i(ξ_s)
@@ -1183,6 +1302,8 @@ __device__ __forceinline__ void blkp_ichain_pair_body(const TChainArgs& g, const
   for (int c = role; c < C; c += 2) {
     const int j0 = c * SL;
     double ur[SL][4], ui[SL][4];
+    double2 sk[SL];
+    if constexpr (PEN && !FWD) cw.sources(j0, sk);
     cw.form(ia, Ms, Es, Ts, j0, ur, ui);
     if (c == 0) {
       cw.init(g, xs, b);
@@ -1191,12 +1312,30 @@ __device__ __forceinline__ void blkp_ichain_pair_body(const TChainArgs& g, const
     }
     blkp_wave_sync();
     __builtin_amdgcn_s_setprio(2);
-    cw.steps(ur, ui, xs, Os, j0);
+    cw.steps(ur, ui, xs, Os, j0, sk);
     __builtin_amdgcn_s_setprio(0);
+    if constexpr (PEN && FWD) {
+      if (role == 1 && c + 2 >= C) {  // role 1's last chunk: its sum before the counter
+        const double rs = row_sum16(cw.pen);
+        if (cw.l == 0) *ps = rs;
+      }
+    }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");  // the exchange row is written before the counter
     if ((threadIdx.x & 63) == 0) __hip_atomic_store(flag, c + 1, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
     cw.flush(Os, j0);
     blkp_wave_sync();
+  }
+  if constexpr (PEN && FWD) {
+    if (role == 0) {
+      double rs = row_sum16(cw.pen);
+      if (C >= 2) {
+        const int c1 = C - 1 - (C & 1);  // role 1's last chunk: the largest odd c < C
+        while (__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP) < c1 + 1) __builtin_amdgcn_s_sleep(1);
+        blkp_wave_sync();
+        rs += *ps;
+      }
+      if (cw.l == 0) g.J[b] = g.mu * rs;
+    }
   }
 }
 
@@ -1214,10 +1353,10 @@ static __global__ void k_blkp_phase(const BlkpIntArgs ia, long long n) {
 
 // nseeds seeds from seed0 on; dual: both directions (wave pair 2 s + d: seed seed0 + s, d = 0 forward, 1 μ), else
 // the direction dir alone; every wave passes the coefficients' barrier before it may leave
-template <int SL, bool SYM>
+template <int SL, bool SYM, bool PEN = false>
 __global__ __launch_bounds__(256) void k_blkp_ichain(const TChainArgs gf, const TChainArgs gb, const BlkArgs bk,
                                                      const BlkpIntArgs ia, int seed0, int nseeds, int dual, int dir,
-                                                     const int* stale) {
+                                                     const int* stale, const BlkpPen pp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   if (stale && *stale != 0) return;  // uniform over the grid
   double2* const Ms = reinterpret_cast<double2*>(smem);
@@ -1229,8 +1368,8 @@ __global__ __launch_bounds__(256) void k_blkp_ichain(const TChainArgs gf, const 
   const int p = (int)blockIdx.x * (int)(blockDim.x >> 6) + w;
   if (p >= (dual ? 2 : 1) * nseeds) return;
   const int s = dual ? p >> 1 : p, d = dual ? p & 1 : dir;
-  if (d == 0) blkp_ichain_body<true, SL, SYM>(gf, bk, ia, Ms, xs, seed0 + s);
-  else blkp_ichain_body<false, SL, SYM>(gb, bk, ia, Ms, xs, seed0 + s);
+  if (d == 0) blkp_ichain_body<true, SL, SYM, PEN>(gf, bk, ia, Ms, xs, seed0 + s, pp);
+  else blkp_ichain_body<false, SL, SYM, PEN>(gb, bk, ia, Ms, xs, seed0 + s, pp);
 }
 
 // the paired form: npw pairs per workgroup of 2 npw waves (blockDim.x = 128 npw), pair (w, w + npw) = (seed,
@@ -1244,10 +1383,10 @@ __host__ __device__ inline size_t blkp_ipair_lds(int D, int SL, bool sym, int np
   return ((size_t)(D + 1) * (sym ? 128 : 256) + (size_t)npw * 34 + 2 * (size_t)npw * blkp_ipair_wave_lds(SL, sym, D)) *
          sizeof(double2);
 }
-template <int SL, bool SYM>
+template <int SL, bool SYM, bool PEN = false>
 __global__ __launch_bounds__(512) void k_blkp_ichain2(const TChainArgs gf, const TChainArgs gb, const BlkArgs bk,
                                                       const BlkpIntArgs ia, int seed0, int nseeds, int dual, int dir,
-                                                      const int* stale) {
+                                                      const int* stale, const BlkpPen pp) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   if (stale && *stale != 0) return;  // uniform over the grid
   double2* const Ms = reinterpret_cast<double2*>(smem);
@@ -1255,16 +1394,17 @@ __global__ __launch_bounds__(512) void k_blkp_ichain2(const TChainArgs gf, const
   const double2* const src = SYM ? ia.Msym : ia.M;
   for (int e = tid; e < msz; e += blockDim.x) Ms[e] = src[e];
   const int npw = (int)(blockDim.x >> 7), pw = w % npw;
-  double2* const pr = Ms + msz + 34 * pw;  // the pair's exchange row (32) and counter
+  double2* const pr = Ms + msz + 34 * pw;  // the pair's exchange row (32), counter and (PEN) role 1's penalty sum
   int* const flag = reinterpret_cast<int*>(pr + 32);
+  double* const ps = reinterpret_cast<double*>(pr + 33);
   if (w < npw && (tid & 63) == 0) *flag = 0;
   __syncthreads();
   double2* const wl = Ms + msz + npw * 34 + (size_t)w * blkp_ipair_wave_lds(SL, SYM, D);
   const int p = (int)blockIdx.x * npw + pw;
   if (p >= (dual ? 2 : 1) * nseeds) return;  // both waves of the pair
   const int s = dual ? p >> 1 : p, d = dual ? p & 1 : dir;
-  if (d == 0) blkp_ichain_pair_body<true, SL, SYM>(gf, bk, ia, Ms, pr, flag, wl, w / npw, seed0 + s);
-  else blkp_ichain_pair_body<false, SL, SYM>(gb, bk, ia, Ms, pr, flag, wl, w / npw, seed0 + s);
+  if (d == 0) blkp_ichain_pair_body<true, SL, SYM, PEN>(gf, bk, ia, Ms, pr, flag, ps, wl, w / npw, seed0 + s, pp);
+  else blkp_ichain_pair_body<false, SL, SYM, PEN>(gb, bk, ia, Ms, pr, flag, ps, wl, w / npw, seed0 + s, pp);
 }
 
 // ---- the order-3 gradient on the stored states (the reference's expm_jacobian! + _compute_u_sensitivity,
@@ -1281,7 +1421,7 @@ struct BlkpGradArgs {
   const cx<double>* A;       // (nu+1) N x N unshifted generators, column-major
   const double* u;           // B x Nt x nu
   const cx<double>* X;       // B x (Nt+1) x N x m states
-  const cx<double>* L;       // μ_k, same layout
+  const cx<double>* L;       // μ_k (k_blkp_grad<NU, true>: λ_k), same layout
   const cx<double>* coef;    // B x 2m λ_N coefficients
   double* dJdu;              // B x Nt x nu
   long long tiles;           // B ceil(Nt / 16)
@@ -1306,7 +1446,8 @@ __device__ __forceinline__ void blkp_axpy(CMat& Y, double a, const CMat& X) {  /
   }
 }
 
-template <int NU>
+// LAM: L holds λ_k itself (the penalised / sourced backward chains), no coefficients applied
+template <int NU, bool LAM = false>
 __global__ __launch_bounds__(256, 2) void k_blkp_grad(const BlkpGradArgs a) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   if (a.stale && *a.stale != 0) return;
@@ -1387,7 +1528,7 @@ __global__ __launch_bounds__(256, 2) void k_blkp_grad(const BlkpGradArgs a) {
         return cm_mul<false>(op(q + 1, form), M, M);
       };
       for (int c = 0; c < m; ++c) {
-        const cx<double> cf = a.coef[(size_t)b * 2 * m + c];
+        const cx<double> cf = LAM ? cx<double>{1.0, 0.0} : a.coef[(size_t)b * 2 * m + c];
         const cx<double>* xb = a.X + ((size_t)b * (Nt + 1) + kc) * Nm + (size_t)c * N;  // x_k
         const cx<double>* lb = a.L + ((size_t)b * (Nt + 1) + kc + 1) * Nm + (size_t)c * N;  // μ_{k+1}
         CMat X, Lm;
@@ -1398,8 +1539,8 @@ __global__ __launch_bounds__(256, 2) void k_blkp_grad(const BlkpGradArgs a) {
           const cx<double> mv = ok ? lb[rows[e]] : cx<double>{0.0, 0.0};
           X.r[e] = xv.r;
           X.i[e] = xv.i;
-          Lm.r[e] = cf.r * mv.r - cf.i * mv.i;
-          Lm.i[e] = cf.r * mv.i + cf.i * mv.r;
+          Lm.r[e] = LAM ? mv.r : cf.r * mv.r - cf.i * mv.i;
+          Lm.i[e] = LAM ? mv.i : cf.r * mv.i + cf.i * mv.r;
         }
         // the co-state side: Q_1 = A_k^H λ, Q_2 = A_k^H Q_1
         CMat Q1 = cm_mul<false>(op(0, 1), Lm, Lm);

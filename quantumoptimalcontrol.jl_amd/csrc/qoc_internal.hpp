@@ -186,6 +186,7 @@ struct qoc_ctx {
   size_t blkp_ph_n = 0;
   int ichain_last = 0;               // 0: no, 1: every entry, 2: the symmetric propagators' upper triangle
   bool ichain_fwd = false;
+  int blkp_fwd_nwb = 0;              // the wave blocks blkp_forward ran on (the live ones, or all with a co-state source)
   double* d_blkp_ctab = nullptr; // the Chebyshev form's coefficient table (qoc_blkp.hpp blkp_cheb), for ctab_cm / ctab_rmax
   int ctab_cm = 0;
   double ctab_rmax = 0.0;

@@ -329,13 +329,17 @@ static size_t blk_lds_of(const qoc_ctx* c, int nwb = -1) {
 // the dead rows' zeros into the state-shaped buffers, so every output (x_k, λ_k, J, dJ/du) is what the full launch
 // gives.  The tunable bus (m = 1, |110> -> |200>) carries its state in the 14-row even-parity block only.
 // QOC_BLK_DEAD=0 launches every block.  Sets bk.wrow / bk.nwb; leaves them when every block is live.
-static int blk_live(qoc_ctx* c, BlkArgs& bk) {
-  if (!blk_big(c) || c->h_wrow.empty() || c->h_Xt.empty() || !c->have_x0) return QOC_OK;
+// blk_live_rows: the host half: the live wave blocks' rows (16 per block) and the dead blocks' rows; false: every block
+// counts as live
+static bool blk_live_rows(const qoc_ctx* c, std::vector<int>& wl, std::vector<int>& dead) {
+  wl.clear();
+  dead.clear();
+  if (!blk_big(c) || c->h_wrow.empty() || c->h_Xt.empty() || !c->have_x0) return false;
   const char* env = getenv("QOC_BLK_DEAD");
-  if (env && atoi(env) == 0) return QOC_OK;
+  if (env && atoi(env) == 0) return false;
   const int N = c->N, mu = c->m_user;
   const size_t cnt = c->x0_per_seed ? (size_t)c->B : 1, Nmu = (size_t)N * mu;
-  if (c->h_x0.size() < 2 * Nmu * cnt || c->h_Xt.size() < 2 * Nmu) return QOC_OK;
+  if (c->h_x0.size() < 2 * Nmu * cnt || c->h_Xt.size() < 2 * Nmu) return false;
   std::vector<char> live(N, 0);
   auto mark = [&](const double* v) {
     for (size_t e = 0; e < Nmu; ++e)
@@ -343,7 +347,6 @@ static int blk_live(qoc_ctx* c, BlkArgs& bk) {
   };
   for (size_t q = 0; q < cnt; ++q) mark(c->h_x0.data() + 2 * Nmu * q);
   mark(c->h_Xt.data());
-  std::vector<int> wl, dead;
   for (int w = 0; w < c->nwb; ++w) {
     bool lv = false;
     for (int i = 0; i < 16; ++i) {
@@ -356,7 +359,12 @@ static int blk_live(qoc_ctx* c, BlkArgs& bk) {
       else if (r >= 0) dead.push_back(r);
     }
   }
-  if (dead.empty() || wl.empty()) return QOC_OK;
+  return !(dead.empty() || wl.empty());
+}
+// all: every block counts as live (a co-state source puts λ_k on every row)
+static int blk_live(qoc_ctx* c, BlkArgs& bk, bool all = false) {
+  std::vector<int> wl, dead;
+  if (all || !blk_live_rows(c, wl, dead)) return QOC_OK;
   if (wl != c->h_wrow_live || dead != c->h_dead_rows) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     for (int** p : {&c->d_wrow_live, &c->d_dead_rows})
@@ -397,6 +405,43 @@ static int blk_zero_dead(qoc_ctx* c, std::initializer_list<void*> bufs) {
   c->dead_dirty = false;
   return QOC_OK;
 }
+// The state penalty as the stored / interpolating propagator chains take it (qoc_blkp.hpp BlkpPen) for the wave blocks
+// `wrow` (16 rows each): the row masks from h_pen_rows, the column mask from h_pen_cols.  False: no penalised entry
+// there (μ = 0, no column, or every penalised row in a dead block, whose x_k is zero): the eval is the unpenalised one.
+static bool blkp_pen_masks(const qoc_ctx* c, const std::vector<int>& wrow, BlkpPen& pp) {
+  pp = BlkpPen{};
+  if (c->mu == 0.0 || wrow.size() > 16 * 8) return false;
+  unsigned rows = 0;
+  for (size_t e = 0; e < wrow.size(); ++e)
+    if (wrow[e] >= 0 && std::find(c->h_pen_rows.begin(), c->h_pen_rows.end(), wrow[e]) != c->h_pen_rows.end()) {
+      pp.prow[e / 16] |= (unsigned short)(1u << (e % 16));
+      rows |= 1u;
+    }
+  for (int col : c->h_pen_cols)
+    if (col >= 0 && col < std::min(c->m, 32)) pp.pcol |= 1u << col;
+  return rows != 0 && pp.pcol != 0;
+}
+// the masks for the layout an eval runs on: every block with a co-state source (λ_k is then nonzero on every row),
+// else the live blocks
+static bool blkp_pen_active(const qoc_ctx* c, BlkpPen& pp) {
+  std::vector<int> wl, dead;
+  const bool part = !c->src_on && blk_live_rows(c, wl, dead);
+  return blkp_pen_masks(c, part ? wl : c->h_wrow, pp);
+}
+// How a state penalty / co-state source runs on blocks of 5..16 rows:
+//   0  none in effect (μ = 0 or no penalised entry in a live block, and no source): the unpenalised paths, same bits;
+//   1  on the stored / interpolating propagator chains' PEN instantiations (blkp_forward, then blkp_backward);
+//   2  on the Chebyshev block chains (QOC_BLKP_PEN=0, read per call; packed states; QOC_BLKP=0).
+static int blkp_pen_mode(const qoc_ctx* c) {
+  if (c->mu == 0.0 && !c->src_on) return 0;
+  const char* env = getenv("QOC_BLKP_PEN");
+  if ((env && atoi(env) == 0) || c->packed || !blkp_on(c)) return 2;
+  if (c->src_on) return 1;
+  BlkpPen pp;
+  return blkp_pen_active(c, pp) ? 1 : 0;
+}
+static bool blkp_fits_nwb(const qoc_ctx* c, int nwb);
+
 // dynamic LDS above the 64 KiB default (up to 16 MFMA block waves of staging)
 template <typename K>
 static hipError_t blk_lds_attr(K kern, size_t lds) {
@@ -505,12 +550,15 @@ int blk_backward(qoc_ctx* c, int order, double* d_dJdu) {
 }
 
 // qoc_eval_dev with a built-in cost, no penalty and no co-state source: the forward chain and the μ recurrence
-// (λ_k = coef ⊙ μ_k, src/penalty_fcns.jl:19-22, 35-40) in one launch, then the gradient with the coefficients.
+// (λ_k = coef ⊙ μ_k, src/penalty_fcns.jl:19-22, 35-40) in one launch, then the gradient with the coefficients.  (With a
+// penalty or a source λ_k needs x_k: the two directions run in sequence, qoc_propagate_dev then the backward.)
 bool blk_concurrent_ok(const qoc_ctx* c, int order) {
   // MFMA block waves: the contraction from the chains' captures (k_grad_rr_c, order 3)
   if (blk_big(c) && !(order == 3 && tchain_cap_ok(c))) return false;
+  // (blocks of 5..16 rows: a penalty without a penalised entry in a live block is no penalty, blkp_pen_mode)
   return blk_active(c) && c->concurrent && order >= 1 && order <= BLK_ORDMAX &&
-         (c->cost_kind == QOC_COST_TRACE || c->cost_kind == QOC_COST_ZCAL) && c->mu == 0.0 && !c->src_on;
+         (c->cost_kind == QOC_COST_TRACE || c->cost_kind == QOC_COST_ZCAL) &&
+         ((c->mu == 0.0 && !c->src_on) || (blkp_on(c) && blkp_pen_mode(c) == 0));
 }
 
 // ---- stored propagators for blocks of 5..16 rows (qoc_blkp.hpp) ------------------------------------------------------
@@ -1036,22 +1084,26 @@ static int blkp_launch_exp(qoc_ctx* c, BlkpPlan& pl, long long unit0, long long 
   return QOC_OK;
 }
 // one direction's chains for seeds [s0, s1) from the propagators in U (seed useed0's first)
+// (pp: the PEN instantiation -- the forward's penalty sum, the backward's λ chain with sources --, or nullptr)
 template <bool FWD>
 static int blkp_launch_chain(qoc_ctx* c, const BlkpPlan& pl, const TChainArgs& g, const BlkArgs& bk, const double2* U,
-                             int s0, int s1, int useed0, hipStream_t st, const int* stale) {
-  auto chain = pl.ch == 8   ? k_blkp_chain<FWD, 8>
-               : pl.ch == 4 ? k_blkp_chain<FWD, 4>
-               : pl.ch == 2 ? k_blkp_chain<FWD, 2>
-                            : k_blkp_chain<FWD, 1>;
+                             int s0, int s1, int useed0, hipStream_t st, const int* stale, const BlkpPen* pp = nullptr) {
+  auto chain = pl.ch == 8   ? (pp ? k_blkp_chain<FWD, 8, true> : k_blkp_chain<FWD, 8>)
+               : pl.ch == 4 ? (pp ? k_blkp_chain<FWD, 4, true> : k_blkp_chain<FWD, 4>)
+               : pl.ch == 2 ? (pp ? k_blkp_chain<FWD, 2, true> : k_blkp_chain<FWD, 2>)
+                            : (pp ? k_blkp_chain<FWD, 1, true> : k_blkp_chain<FWD, 1>);
   HIPCHK(c, blk_lds_attr(chain, pl.clds));
   const int mk = mark_begin(c, FWD ? 1 : 2, st);
-  hipLaunchKernelGGL(chain, dim3(s1 - s0), dim3(64 * bk.nwb * c->m), pl.clds, st, g, bk, U, s0, useed0, stale);
+  hipLaunchKernelGGL(chain, dim3(s1 - s0), dim3(64 * bk.nwb * c->m), pl.clds, st, g, bk, U, s0, useed0, stale,
+                     pp ? *pp : BlkpPen{});
   mark_end(c, mk, st);
   HIPCHK(c, hipGetLastError());
   return QOC_OK;
 }
 // the order-3 gradient from x_k, μ_{k+1} and the λ_N coefficients
-static int blkp_launch_grad(qoc_ctx* c, const BlkArgs& bk, double* d_dJdu, const int* stale, cx<double>* coef_out) {
+// (lam: d_L holds λ_k itself, the PEN backward chains')
+static int blkp_launch_grad(qoc_ctx* c, const BlkArgs& bk, double* d_dJdu, const int* stale, cx<double>* coef_out,
+                            bool lam = false) {
   BlkpGradArgs ga{};
   ga.N = c->N;
   ga.m = c->m;
@@ -1086,7 +1138,7 @@ static int blkp_launch_grad(qoc_ctx* c, const BlkArgs& bk, double* d_dJdu, const
     }
   }
   const size_t glds = blkp_grad_lds(bk.nwb, c->nu);
-  auto gk = c->nu == 1 ? k_blkp_grad<1> : k_blkp_grad<2>;
+  auto gk = c->nu == 1 ? (lam ? k_blkp_grad<1, true> : k_blkp_grad<1>) : (lam ? k_blkp_grad<2, true> : k_blkp_grad<2>);
   HIPCHK(c, blk_lds_attr(gk, glds));
   int gpc = 0;
   if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&gpc, (const void*)gk, 256, glds) != hipSuccess || gpc < 1) gpc = 2;
@@ -1114,8 +1166,10 @@ static int blkp_ichain_on(const qoc_ctx* c, const BlkArgs& bk, const BlkpPlan& p
 // dual: the forward chain and the μ recurrence of every seed (one launch), else direction dir alone; the forward's
 // terminal cost and λ_N coefficients by k_terminal_cost (64 threads: chain_costs as the one-wave chain workgroups run
 // it, the same sums); stale: a queued stale-u flag (nonzero: nothing is written)
+// pp: the PEN instantiations (one direction at a time): the forward leaves the seeds' penalty sums in J, which
+// k_terminal_cost then adds the terminal cost to; the backward is the λ chain with sources
 static int blkp_launch_ichain(qoc_ctx* c, const TChainArgs& gf, const TChainArgs& gb, const BlkArgs& bk,
-                              const BlkpIntArgs& ia0, bool dual, int dir, const int* stale) {
+                              const BlkpIntArgs& ia0, bool dual, int dir, const int* stale, const BlkpPen* pp = nullptr) {
   // the slices' e^{μ(u_k)} first (one sincos per (seed, slice) instead of one per chain wave)
   const size_t nph = (size_t)c->B * c->Nt;
   if (c->blkp_ph_n < nph) {
@@ -1144,20 +1198,22 @@ static int blkp_launch_ichain(qoc_ctx* c, const TChainArgs& gf, const TChainArgs
   if (const char* e = getenv("QOC_BLKP_IPW")) npw = atoi(e) == 4 ? 4 : 2;  // (tests: force either)
   const bool pair = !(getenv("QOC_BLKP_IPAIR") && atoi(getenv("QOC_BLKP_IPAIR")) == 0) &&
                     blkp_ipair_lds(ia.D, BLKP_ISL, sym, npw) <= 160 * 1024;
-  auto kern = pair ? (sym ? k_blkp_ichain2<BLKP_ISL, true> : k_blkp_ichain2<BLKP_ISL, false>)
-                   : (sym ? k_blkp_ichain<BLKP_ISL, true> : k_blkp_ichain<BLKP_ISL, false>);
+  auto kern = pp ? (pair ? (sym ? k_blkp_ichain2<BLKP_ISL, true, true> : k_blkp_ichain2<BLKP_ISL, false, true>)
+                         : (sym ? k_blkp_ichain<BLKP_ISL, true, true> : k_blkp_ichain<BLKP_ISL, false, true>))
+                   : (pair ? (sym ? k_blkp_ichain2<BLKP_ISL, true> : k_blkp_ichain2<BLKP_ISL, false>)
+                           : (sym ? k_blkp_ichain<BLKP_ISL, true> : k_blkp_ichain<BLKP_ISL, false>));
   const size_t lds = pair ? blkp_ipair_lds(ia.D, BLKP_ISL, sym, npw) : blkp_ichain_lds(ia.D, BLKP_ISL, 4, sym);
   HIPCHK(c, blk_lds_attr(kern, lds));
   const int per = pair ? npw : 4;  // (seed, direction) pairs per workgroup
   const int mk = mark_begin(c, dual || dir == 0 ? 1 : 2);
   hipLaunchKernelGGL(kern, dim3((pairs + per - 1) / per), dim3(pair ? 128 * npw : 256), lds, c->stream, gf, gb, bk, ia,
-                     0, c->B, dual ? 1 : 0, dir, stale);
+                     0, c->B, dual ? 1 : 0, dir, stale, pp ? *pp : BlkpPen{});
   mark_end(c, mk);
   HIPCHK(c, hipGetLastError());
   if (dual || dir == 0) {
     hipLaunchKernelGGL(k_terminal_cost<double>, dim3(c->B), dim3(64), 0, c->stream, c->N, c->m, c->Nt,
-                       (const cx<double>*)gf.X, (const cx<double>*)gf.Xt, gf.cost_kind, gf.n_norm, 0, gf.J, gf.coef,
-                       gf.sc);
+                       (const cx<double>*)gf.X, (const cx<double>*)gf.Xt, gf.cost_kind, gf.n_norm, pp ? 1 : 0, gf.J,
+                       gf.coef, gf.sc);
     HIPCHK(c, hipGetLastError());
   }
   return QOC_OK;
@@ -1252,25 +1308,32 @@ static int blkp_eval_concurrent(qoc_ctx* c, double* d_dJdu, const BlkArgs& bk) {
 
 // the stored-propagator eval applies (blocks of 5..16 rows with a live-wave layout that fits the chain and gradient
 // kernels)
-static bool blkp_fits(qoc_ctx* c, const BlkArgs& bk) {
-  const int waves = bk.nwb * c->m;
+static bool blkp_fits_nwb(const qoc_ctx* c, int nwb) {
+  const int waves = nwb * c->m;
   return waves <= 8 && blkp_chain_lds(c->N, c->m, waves, blkp_chunk(waves)) <= 160 * 1024 &&
-         blkp_grad_lds(bk.nwb, c->nu) <= 160 * 1024;
+         blkp_grad_lds(nwb, c->nu) <= 160 * 1024;
 }
+static bool blkp_fits(qoc_ctx* c, const BlkArgs& bk) { return blkp_fits_nwb(c, bk.nwb); }
 
 // propagate on stored propagators (the reference's own structure, src/gradient_computations.jl:17-29): every U_k of
 // the live blocks formed on MFMA, the forward chain from them (seed groups pipelined as in the eval), states in d_X;
-// the propagators stay for grape_sensitivity (every seed's: 4.2 GB at the tunable bus' B = 512).  Built-in costs, no
-// penalty; QOC_BLKP_SPLIT=0 keeps the Chebyshev block chains.  Returns 1 (nothing launched) when it does not apply.
+// the propagators stay for grape_sensitivity (every seed's: 4.2 GB at the tunable bus' B = 512).  Built-in costs; a
+// state penalty's sum is the chains' own (their PEN instantiations; QOC_BLKP_PEN=0: the Chebyshev block chains take a
+// penalised propagate); QOC_BLKP_SPLIT=0 keeps the Chebyshev block chains.  Returns 1 (nothing launched) when it does
+// not apply.
 int blkp_forward(qoc_ctx* c) {
   const char* env = getenv("QOC_BLKP_SPLIT");
-  if ((env && atoi(env) == 0) || !blkp_on(c) || c->mu != 0.0 ||
+  const int pmode = blkp_pen_mode(c);
+  if ((env && atoi(env) == 0) || !blkp_on(c) || (c->mu != 0.0 && pmode == 2) ||
       (c->cost_kind != QOC_COST_TRACE && c->cost_kind != QOC_COST_ZCAL))
     return 1;
   BlkArgs bk = blk_args(c);
-  int r = blk_live(c, bk);
+  int r = blk_live(c, bk, pmode == 1 && c->src_on);  // a co-state source: every block live
   if (r) return r;
   if (!blkp_fits(c, bk)) return 1;
+  // the penalised forward: the chains' PEN instantiations add the penalty sum to J
+  BlkpPen pp;
+  const BlkpPen* const pen = pmode == 1 && blkp_pen_active(c, pp) ? &pp : nullptr;
   const long long per_seed = (long long)c->Nt * bk.nwb;
   const int parts = blkp_parts(c);
   BlkpPlan pl;
@@ -1278,11 +1341,12 @@ int blkp_forward(qoc_ctx* c) {
   const TChainArgs gf = tchain_args(c);
   c->ichain_last = blkp_ichain_on(c, bk, pl);
   c->ichain_fwd = c->ichain_last != 0;
+  c->blkp_fwd_nwb = bk.nwb;
   if (c->ichain_fwd) {  // the forward chain interpolates its propagators; grape_sensitivity's μ recurrence will too
     if (bk.nwb != c->nwb) {
       if ((r = blk_zero_dead(c, {c->d_X, c->d_L}))) return r;
     }
-    if ((r = blkp_launch_ichain(c, gf, gf, bk, pl.ia, false, 0, nullptr))) return r;
+    if ((r = blkp_launch_ichain(c, gf, gf, bk, pl.ia, false, 0, nullptr, pen))) return r;
     c->fwd_captured = false;
     c->props_since_reset++;
     c->steps_stale = true;
@@ -1308,7 +1372,7 @@ int blkp_forward(qoc_ctx* c) {
       HIPCHK(c, hipEventRecord(c->sync_ev[p], c->stream));
       HIPCHK(c, hipStreamWaitEvent(c->stream2, c->sync_ev[p], 0));
     }
-    if ((r = blkp_launch_chain<true>(c, pl, gf, bk, U, s0, s1, 0, cs, nullptr))) return r;
+    if ((r = blkp_launch_chain<true>(c, pl, gf, bk, U, s0, s1, 0, cs, nullptr, pen))) return r;
   }
   if (parts > 1) {
     HIPCHK(c, hipEventRecord(c->sync_ev[parts], c->stream2));
@@ -1322,34 +1386,61 @@ int blkp_forward(qoc_ctx* c) {
 }
 
 bool blkp_backward_ok(const qoc_ctx* c, int order) {
-  return c->fwd_kind == 2 && order == 3 && c->mu == 0.0 && !c->src_on &&
-         (c->cost_kind == QOC_COST_TRACE || c->cost_kind == QOC_COST_ZCAL) && (c->ichain_fwd || c->d_blkU);
+  if (!(c->fwd_kind == 2 && order == 3 && (c->cost_kind == QOC_COST_TRACE || c->cost_kind == QOC_COST_ZCAL) &&
+        (c->ichain_fwd || c->d_blkU)))
+    return false;
+  const int pmode = blkp_pen_mode(c);
+  if (pmode == 2) return false;                                                   // the Chebyshev block chains
+  return !(pmode == 1 && c->src_on && !blkp_fits_nwb(c, c->nwb));  // a co-state source: every block's waves
 }
 
 // grape_sensitivity after blkp_forward: the μ recurrence from the stored propagators (μ_N = X_target, λ_k = coef ⊙ μ_k,
-// src/penalty_fcns.jl:19-22, 35-40), then the order-3 gradient; stale: the device flag of a queued stale-u check
+// src/penalty_fcns.jl:19-22, 35-40), then the order-3 gradient; stale: the device flag of a queued stale-u check.
+// With a state penalty or a co-state source (blkp_pen_mode 1) the chains' PEN instantiations run λ_k itself,
+// λ_N = coef ⊙ X_target + s_N, λ_k = U_k^H λ_{k+1} + s_k (src/gradient_computations.jl:46-58), and the gradient reads it
+// as it is.  A source counts every block live; where the propagate ran on other wave blocks (the live ones alone, or
+// the interpolating chains of one block) the propagators of this layout are formed first, from the propagate's u.
 int blkp_backward(qoc_ctx* c, double* d_dJdu, const int* stale) {
+  const int pmode = blkp_pen_mode(c);
   BlkArgs bk = blk_args(c);
-  int r = blk_live(c, bk);
+  int r = blk_live(c, bk, c->src_on);
   if (r) return r;
   if (!c->d_coef_mu) {
     HIPCHK(c, hipMalloc((void**)&c->d_coef_mu, (size_t)c->B * 2 * c->m_user * sizeof(cx<double>)));
     c->dev_bytes += (size_t)c->B * 2 * c->m_user * sizeof(cx<double>);
   }
+  BlkpPen pp;
+  const bool lam = pmode == 1;
+  if (lam) blkp_pen_active(c, pp);  // (no penalised entry: empty masks, the caller's source alone)
+  const BlkpPen* const pen = lam ? &pp : nullptr;
   TChainArgs gb = tchain_args(c);
-  gb.mu_mode = 1;
+  gb.mu_mode = lam ? 0 : 1;
+  if (bk.nwb != c->blkp_fwd_nwb) {  // the propagators of this layout
+    BlkpPlan pl;
+    if ((r = blkp_plan(c, bk, 1, pl))) return r;
+    const long long units = (long long)c->B * c->Nt * bk.nwb;
+    if ((r = blkp_ensure_store(c, (size_t)units * 256 * sizeof(double2), false))) return r;
+    if ((r = blkp_launch_exp(c, pl, 0, units, (double2*)c->d_blkU, 0))) return r;
+    c->ichain_fwd = false;
+    c->ichain_last = 0;
+    c->blkp_fwd_nwb = bk.nwb;
+  }
+  if (bk.nwb != c->nwb) {  // (a no-op unless a sourced backward left λ on the dead rows)
+    if ((r = blk_zero_dead(c, {c->d_X, c->d_L}))) return r;
+  }
   if (c->ichain_fwd) {  // the propagate interpolated: the μ recurrence from the same coefficients (the same u)
     BlkpIntArgs ia;
     blkp_interp_args(c, bk, ia);
-    if ((r = blkp_launch_ichain(c, gb, gb, bk, ia, false, 1, stale))) return r;
+    if ((r = blkp_launch_ichain(c, gb, gb, bk, ia, false, 1, stale, pen))) return r;
   } else {
     BlkpPlan pl;
     if ((r = blkp_plan(c, bk, 1, pl, false))) return r;
-    if ((r = blkp_launch_chain<false>(c, pl, gb, bk, (const double2*)c->d_blkU, 0, c->B, 0, c->stream, stale)))
+    if ((r = blkp_launch_chain<false>(c, pl, gb, bk, (const double2*)c->d_blkU, 0, c->B, 0, c->stream, stale, pen)))
       return r;
   }
-  if ((r = blkp_launch_grad(c, bk, d_dJdu, stale, c->d_coef_mu))) return r;
-  c->L_is_mu = true;
+  if ((r = blkp_launch_grad(c, bk, d_dJdu, stale, lam ? nullptr : c->d_coef_mu, lam))) return r;
+  if (c->src_on) c->dead_dirty = true;  // λ_k is nonzero on the rows of blocks that carry no state
+  c->L_is_mu = !lam;
   c->last_eval_mode = 7;
   return QOC_OK;
 }
