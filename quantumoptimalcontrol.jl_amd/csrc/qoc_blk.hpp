@@ -760,7 +760,7 @@ __device__ __forceinline__ void blkrot_bwd_body(const TChainArgs& g, const BlkAr
   }
 }
 
-// Zeros on the rows of the blocks that carry no state (qoc_run_blk.hip blk_live): rows[0..nrow) of each of the
+// Zeros on the rows of the blocks that carry no state (qoc_run_blk.hip blk_zero_dead): rows[0..nrow) of each of the
 // `cols` N-row columns of up to six state-shaped buffers (x_k, μ_k and the chains' captured products)
 struct ZeroRows {
   double2* buf[6];

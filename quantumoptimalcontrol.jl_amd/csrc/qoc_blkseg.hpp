@@ -32,7 +32,7 @@
 // traces need two of K's four Pauli components.  z enters once per lane: z^Nt on x_N (the only quantity of phase 2
 // that sees the phase), z̄ on G at the segment's end.
 // Neither x_k, λ_k nor U_k go to HBM: the launch reads u and writes J, the λ_N coefficients and dJdu.  qoc_get_states
-// and qoc_get_costates rebuild x_k / λ_k on demand with the k_blku_* chains (qoc_run_blk.hip).
+// and qoc_get_costates rebuild x_k / λ_k on demand with the k_blku_* chains (qoc_run_blku.hip).
 //
 // The reference's own call form runs the two halves apart: Ipopt's f calls propagate, its f_grad grape_sensitivity
 // (examples/ipopt_callbacks_exp.jl:11-31; f alone in every line-search trial).  MODE splits the launch at the end of

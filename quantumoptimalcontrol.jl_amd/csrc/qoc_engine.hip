@@ -417,7 +417,7 @@ int qoc_create(qoc_ctx** out, int device, int N, int m, int nu, int Nt, int B, i
   // LDS-resident kernels when the problem fits them, the chunked GEMM pipeline otherwise
   const bool small = expm_supported(N, precision) && N <= kChainMaxN &&
                      N <= (precision == QOC_FP64 ? chain_max_n<double>() : chain_max_n<float>()) && N * m <= 4 * CHAIN_THREADS;
-  const bool force_big = getenv("QOC_FORCE_LARGE_N") && atoi(getenv("QOC_FORCE_LARGE_N")) != 0;
+  const bool force_big = env_int("QOC_FORCE_LARGE_N", 0) != 0;
   if ((!small || force_big) && nu > 8)
     return fail(nullptr, QOC_ERR_UNSUPPORTED, "large-N path supports nu <= 8 (got %d)", nu);
   qoc_ctx* c = new qoc_ctx();
@@ -470,8 +470,8 @@ int qoc_create(qoc_ctx** out, int device, int N, int m, int nu, int Nt, int B, i
     int ncu = 0;
     if (hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, device) == hipSuccess && ncu > 0) c->ncu = ncu;
   }
-  const bool env_kernel = getenv("QOC_GRAD_KERNEL") && atoi(getenv("QOC_GRAD_KERNEL")) != 0;
-  const bool env_gemm = getenv("QOC_GRAD_GEMM") && atoi(getenv("QOC_GRAD_GEMM")) != 0;
+  const bool env_kernel = env_int("QOC_GRAD_KERNEL", 0) != 0;
+  const bool env_gemm = env_int("QOC_GRAD_GEMM", 0) != 0;
   const size_t grr_lds = (size_t)2 * (nu + 1) * N * (precision == QOC_FP64 ? (N | 1) : ((N + 3) & ~3)) *
                          (precision == QOC_FP64 ? 8 : 4);
   c->grad_rr_any_m = !c->big && N <= 48 && (nu == 1 || nu == 2) && grr_lds <= 160 * 1024 && !env_kernel && !env_gemm;
@@ -517,7 +517,7 @@ int qoc_create(qoc_ctx** out, int device, int N, int m, int nu, int Nt, int B, i
     long long ch = std::max<long long>(1, (long long)(budget / per_item));
     ch = std::min<long long>(ch, units);
     ch = std::min<long long>(ch, 16384);
-    if (getenv("QOC_CHUNK")) ch = std::max(1, std::min<int>(atoi(getenv("QOC_CHUNK")), (int)std::min<long long>(units, 16384)));
+    if (env_set("QOC_CHUNK")) ch = std::max(1, std::min<int>(env_int("QOC_CHUNK", 0), (int)std::min<long long>(units, 16384)));
     c->chunk = (int)ch;
     if ((e = hipMalloc(&c->d_ws, (size_t)ch * per_item)) != hipSuccess) return bail(e, "hipMalloc (workspace)");
     if ((e = hipMalloc((void**)&c->d_red, ((size_t)ch + 8) * sizeof(double))) != hipSuccess)
@@ -526,19 +526,17 @@ int qoc_create(qoc_ctx** out, int device, int N, int m, int nu, int Nt, int B, i
   }
   hipMemset(c->d_pmask, 0, Nm);
   hipMemset(c->d_hist, 0, 13 * 64 * sizeof(unsigned long long));
-  c->chain_cb_fwd = getenv("QOC_CHAIN_CB_FWD") ? atoi(getenv("QOC_CHAIN_CB_FWD")) : 0;
-  c->chain_cb_bwd = getenv("QOC_CHAIN_CB_BWD") ? atoi(getenv("QOC_CHAIN_CB_BWD")) : 0;
-  c->expm_ps = getenv("QOC_EXPM_PS") && atoi(getenv("QOC_EXPM_PS")) != 0;
-  c->expm_alg = (getenv("QOC_EXPM_PADE") && atoi(getenv("QOC_EXPM_PADE")) != 0) ? 0
-                : (getenv("QOC_EXPM_LDS") && atoi(getenv("QOC_EXPM_LDS")) != 0)   ? 2
-                                                                                   : 1;
-  c->ode_kernel = (getenv("QOC_ODE_LDS") && atoi(getenv("QOC_ODE_LDS")) != 0) ? 1 : 0;
-  if (getenv("QOC_BWD_CHUNKS")) c->bwd_chunks = std::max(1, atoi(getenv("QOC_BWD_CHUNKS")));
-  if (getenv("QOC_BWD_LAST")) c->bwd_last_frac = atof(getenv("QOC_BWD_LAST"));
-  if (getenv("QOC_BWD_PRIO")) c->bwd_prio = atoi(getenv("QOC_BWD_PRIO"));
-  if (getenv("QOC_BWD_PRESTATE")) c->bwd_prestate = atoi(getenv("QOC_BWD_PRESTATE"));
-  if (getenv("QOC_CONCURRENT")) c->concurrent = std::max(0, std::min(2, atoi(getenv("QOC_CONCURRENT"))));
-  if (getenv("QOC_TCHAIN_ROT")) c->tchain_rot = atoi(getenv("QOC_TCHAIN_ROT"));
+  c->chain_cb_fwd = env_int("QOC_CHAIN_CB_FWD", 0);
+  c->chain_cb_bwd = env_int("QOC_CHAIN_CB_BWD", 0);
+  c->expm_ps = env_int("QOC_EXPM_PS", 0) != 0;
+  c->expm_alg = env_int("QOC_EXPM_PADE", 0) != 0 ? 0 : env_int("QOC_EXPM_LDS", 0) != 0 ? 2 : 1;
+  c->ode_kernel = env_int("QOC_ODE_LDS", 0) != 0 ? 1 : 0;
+  if (env_set("QOC_BWD_CHUNKS")) c->bwd_chunks = std::max(1, env_int("QOC_BWD_CHUNKS", 0));
+  c->bwd_last_frac = env_dbl("QOC_BWD_LAST", c->bwd_last_frac);
+  c->bwd_prio = env_int("QOC_BWD_PRIO", c->bwd_prio);
+  c->bwd_prestate = env_int("QOC_BWD_PRESTATE", c->bwd_prestate);
+  if (env_set("QOC_CONCURRENT")) c->concurrent = std::max(0, std::min(2, env_int("QOC_CONCURRENT", 0)));
+  c->tchain_rot = env_int("QOC_TCHAIN_ROT", c->tchain_rot);
   hipMemset(c->d_L, 0, (size_t)B * (Nt + 1) * Nm * c->esz);
   *out = c;
   return QOC_OK;
@@ -634,7 +632,7 @@ int qoc_set_generators(qoc_ctx* c, const double* A0, const double* const* Aj) {
     c->expm_run = (c->expm_alg == 1 && nrm > 4.0 * kTheta12 && !c->expm_ps) ? 0 : c->expm_alg;
   }
   c->big_rho_ok = false;
-  if (c->big && !(getenv("QOC_BIG_NORM1") && atoi(getenv("QOC_BIG_NORM1")) != 0)) {
+  if (c->big && env_int("QOC_BIG_NORM1", 0) == 0) {
     // large-N path: 2-norm bounds of skew-Hermitian generators (ρ_j = ||A_j||_2) for the Taylor degree choice
     bool skew = true;
     for (int j = 0; j <= c->nu && skew; ++j) {
@@ -660,8 +658,7 @@ int qoc_set_generators(qoc_ctx* c, const double* A0, const double* const* Aj) {
   }
   if (c->tchain_ok) {  // shifted generators Ã_j = A_j - μ_j I and their norms for the Taylor-action chains
     tchain_thresholds(c->tprm, c->prec);
-    const char* capenv = getenv("QOC_CAPTURE");
-    c->cap_ok = c->prec == QOC_FP64 && !(capenv && atoi(capenv) == 0);
+    c->cap_ok = c->prec == QOC_FP64 && env_int("QOC_CAPTURE", 1) != 0;
     c->tprm.pmin = c->cap_ok ? 2 : 1;  // the captured products are the first two of every slice
     // Chebyshev needs every Ã_j skew-Hermitian (A_j^H = -A_j, Schrödinger generators -i H Δt), so that
     // Ã_k = -i H̃_k has its spectrum on the imaginary axis within the bound ρ_k
@@ -721,16 +718,14 @@ int qoc_set_generators(qoc_ctx* c, const double* A0, const double* const* Aj) {
     }
     if (r != QOC_OK) return r;
     c->cheb_ok = skew;
-    const char* poly = getenv("QOC_TCHAIN_POLY");
-    c->cheb = skew && !(poly && !std::strcmp(poly, "taylor"));
+    c->cheb = skew && !env_is("QOC_TCHAIN_POLY", "taylor");
     // Taylor action by default while the slices need moderately many terms: Chebyshev (fp64, skew-Hermitian)
     // up to ρ_0 = 25 without substeps (cavity 0.15, zz 0.05, tunable bus 9.1: measured faster than Padé-13
     // propagators there too), the Taylor variant while ||Ã_0||_1 <= 1; larger norms form propagators on MFMA
     const bool cheb_run = c->cheb && tchain_mf(c);
-    const char* env = getenv("QOC_CHAIN");
     if (c->chain_req != QOC_CHAIN_AUTO) c->chain_mode = c->chain_req;
-    else if (env && !std::strcmp(env, "taylor")) c->chain_mode = 1;
-    else if (env && !std::strcmp(env, "expm")) c->chain_mode = 0;
+    else if (env_is("QOC_CHAIN", "taylor")) c->chain_mode = 1;
+    else if (env_is("QOC_CHAIN", "expm")) c->chain_mode = 0;
     else c->chain_mode = (cheb_run ? c->tprm.rad[0] <= 25.0 : c->tprm.nrm[0] <= 1.0) ? 1 : 0;
   } else {
     c->chain_mode = 0;

@@ -8,7 +8,9 @@
 //   qoc_run_grad.hip      the fused order-3 gradient (k_grad_rr_*)
 //   qoc_run_big.hip       the large-N GEMM pipeline, the GEMM-shaped gradient and the Fréchet gradient
 //   qoc_run_ode.hip       the Tsit5 path
-//   qoc_run_blk.hip       the block chains and block gradient (generators with small invariant blocks)
+//   qoc_run_blk.hip       the block chains and block gradient (generators with small invariant blocks), their router
+//   qoc_run_blkp.hip      blocks of 5..16 rows on stored / interpolating propagators
+//   qoc_run_blku.hip      blocks of <= 4 rows on block propagators
 //   qoc_run_blkseg.hip    the segmented block eval (blocks of <= 3 rows: one launch for J and dJdu)
 // Each kernel template is launched from one translation unit only; the context (qoc_ctx) and the entry points
 // between the units are declared here.
@@ -21,6 +23,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -30,6 +33,9 @@
 #include "qoc_comm.hpp"
 #include "qoc_tchain.hpp"
 
+namespace qoc {
+struct BlkArgs;  // qoc_blk.hpp
+}
 using namespace qoc;
 
 // launch shape of the segmented block eval (qoc_run_blkseg.hip blkseg_shape)
@@ -293,6 +299,24 @@ int fail(qoc_ctx* ctx, int code, const char* fmt, ...);
 
 constexpr int kChainMaxN = 64;
 
+// The one way to read a switch from the environment (one lookup each: several sit on the per-call path).  env_set: the
+// variable exists; env_int / env_dbl: its atoi / atof when it does, else dflt; env_is: it exists and is exactly one of
+// the literals.
+static inline bool env_set(const char* name) { return getenv(name) != nullptr; }
+static inline int env_int(const char* name, int dflt) {
+  const char* e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+static inline double env_dbl(const char* name, double dflt) {
+  const char* e = getenv(name);
+  return e ? atof(e) : dflt;
+}
+template <typename... L>
+static inline bool env_is(const char* name, L... lits) {
+  const char* e = getenv(name);
+  return e && (... || !std::strcmp(e, lits));
+}
+
 // ---- qoc_engine.hip: staging, packed states, timing marks, dispatch ----
 int upload(qoc_ctx* ctx, const double* host, void* dev, size_t nelem);
 int download(qoc_ctx* ctx, const void* dev, double* host, size_t nelem);
@@ -376,20 +400,35 @@ int tchain_prep(qoc_ctx* c);
 int blk_detect(qoc_ctx* c);
 bool blk_active(const qoc_ctx* c);
 bool blk_rot(const qoc_ctx* c);
-bool blku_on(const qoc_ctx* c);
+bool blku_on(const qoc_ctx* c);  // blocks of <= 4 rows on block propagators (qoc_blku.hpp)
 bool blkp_on(const qoc_ctx* c);  // blocks of 5..16 rows: the concurrent eval on stored propagators (qoc_blkp.hpp)
-int blku_costates(qoc_ctx* c);  // qoc_get_costates after the fused block backward
 int blk_forward(qoc_ctx* c);
 int blk_backward(qoc_ctx* c, int order, double* d_dJdu);
 bool blk_concurrent_ok(const qoc_ctx* c, int order);
 int blk_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu);
-int blku_states(qoc_ctx* c);      // rebuild x_k after a segmented eval (no-op unless X_lazy)
+int blk_materialize(qoc_ctx* c);  // rebuild every lazily kept x_k / λ_k (before a setter changes what they need)
+// blocks of 5..16 rows that carry no state: the live wave blocks' rows and the dead rows (false: every block is live),
+// the launch layout of the live blocks (all: every block counts), the dead rows' zeros by k_zero_rows
+bool blk_live_rows(const qoc_ctx* c, std::vector<int>& wl, std::vector<int>& dead);
+int blk_live(qoc_ctx* c, BlkArgs& bk, bool all = false);
+int blk_zero_dead(qoc_ctx* c, std::initializer_list<void*> bufs);
+
+// ---- qoc_run_blkp.hip ----
+int blkp_pen_mode(const qoc_ctx* c);  // a penalty / co-state source: 0 none in effect, 1 the PEN chains, 2 Chebyshev
+bool blkp_fits_nwb(const qoc_ctx* c, int nwb);
+int blkp_eval_concurrent(qoc_ctx* c, double* d_dJdu, const BlkArgs& bk);  // 1: the propagators do not fit in HBM
 // the reference's split call form for blocks of 5..16 rows on stored propagators: propagate = formation + forward
 // chain (1: not applicable), grape_sensitivity = the μ recurrence + the order-3 gradient
 int blkp_forward(qoc_ctx* c);
 bool blkp_backward_ok(const qoc_ctx* c, int order);
 int blkp_backward(qoc_ctx* c, double* d_dJdu, const int* stale);
-int blk_materialize(qoc_ctx* c);  // rebuild every lazily kept x_k / λ_k (before a setter changes what they need)
+
+// ---- qoc_run_blku.hip ----
+int blku_forward(qoc_ctx* c);
+int blku_backward(qoc_ctx* c, int order, double* d_dJdu);
+int blku_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu);
+int blku_states(qoc_ctx* c);    // rebuild x_k after a segmented eval (no-op unless X_lazy)
+int blku_costates(qoc_ctx* c);  // qoc_get_costates after the fused block backward
 
 // ---- qoc_run_blkseg.hip ----
 // the segmented block eval (qoc_blkseg.hpp): one launch for J and dJdu, x_k / λ_k rebuilt on demand

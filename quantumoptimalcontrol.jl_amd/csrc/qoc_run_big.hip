@@ -68,7 +68,7 @@ int big_gemm(qoc_ctx* c, int opa, int opb, GemmArgs g, int mode = 0) {
     (void)hipEventRecord(gm.a, c->stream);
   }
   // fp32 products with K % 16 == 0 and even M, Ncol: the LDS-DMA staged kernel (QOC_BGEMM_GLDS=0 keeps k_bgemm)
-  static const bool glds_env = !(getenv("QOC_BGEMM_GLDS") && atoi(getenv("QOC_BGEMM_GLDS")) == 0);
+  static const bool glds_env = env_int("QOC_BGEMM_GLDS", 1) != 0;
   const bool glds = std::is_same<T, float>::value && mode == 0 && glds_env && g.K >= 16 && g.K % 16 == 0 && g.M % 2 == 0 &&
                     g.Ncol % 2 == 0 && g.M >= 2 && g.Ncol >= 2;
   if (glds) {
@@ -227,8 +227,8 @@ int taylor_gemm_chunk(qoc_ctx* c, int N, int cnt, void* ws, size_t ws_items, con
   // fp32) need no squaring
   const double th8 = sizeof(T) == 4 ? kTheta8_32 : kTheta8_64;
   const int s8 = nA > th8 ? (int)std::ceil(std::log2(nA / th8)) : 0;
-  const bool t12ok = !getenv("QOC_BIG_NO_T12");
-  if (3 + s8 < best && (!t12ok || 3 + s8 <= 4 + s12) && !getenv("QOC_BIG_NO_T8"))
+  const bool t12ok = !env_set("QOC_BIG_NO_T12");
+  if (3 + s8 < best && (!t12ok || 3 + s8 <= 4 + s12) && !env_set("QOC_BIG_NO_T8"))
     return t8_gemm_chunk<T>(c, N, cnt, ws, ws_items, Asrc, dest, s8, count_hist);
   if (4 + s12 < best && t12ok) return t12_gemm_chunk<T>(c, N, cnt, ws, ws_items, Asrc, dest, s12, count_hist);
   if (count_hist) c->big_thist[(tr - 2) * 64 + std::min(ts, 63)] += cnt;
@@ -590,7 +590,7 @@ int big_backward(qoc_ctx* c, int order, double* d_dJdu) {
   // as five products (G: N^2 m flops; T1 = G Y, S = Y G + T1, R = T1 Y/6 + G + S/2, M' = Y S/6 + R: N^3 each)
   // instead of seven N^2 m-GEMM equivalents; cheaper when 4 N < 6 m (synthetic: m = N).
   bool sandwich = o == 3 && 4 * N < 6 * m;
-  if (const char* s = getenv("QOC_GRAD_SANDWICH")) sandwich = o == 3 && atoi(s) != 0;
+  if (env_set("QOC_GRAD_SANDWICH")) sandwich = o == 3 && env_int("QOC_GRAD_SANDWICH", 0) != 0;
   for (long long u0 = 0; u0 < units; u0 += c->chunk) {
     const int cnt = (int)std::min<long long>(c->chunk, units - u0);
     if (int r = form_norm<T>(c, u0, cnt, (cx<T>*)((char*)c->d_ws + offX * esz), nullptr)) return r;

@@ -44,11 +44,10 @@ static const BlksegShape& blkseg_shape(const qoc_ctx* c) {
   BlksegShape& s = c->seg_shape;
   s = BlksegShape{};
   const int per_cu = std::max(1, std::min(8, (c->B + c->ncu - 1) / std::max(1, c->ncu)));
-  s.W = std::max(1, 8 / per_cu);
-  if (const char* env = getenv("QOC_BLKSEG_W")) s.W = std::max(1, std::min(8, atoi(env)));
+  s.W = std::max(1, std::min(8, env_int("QOC_BLKSEG_W", 8 / per_cu)));
   s.UPW = 64 / std::max(1, c->nblk);
   int S = std::max(1, std::min(s.W * s.UPW, c->Nt));
-  if (const char* env = getenv("QOC_BLKSEG_S")) S = std::max(1, std::min(S, atoi(env)));
+  S = std::max(1, std::min(S, env_int("QOC_BLKSEG_S", S)));
   s.L = (c->Nt + S - 1) / S;
   s.S = (c->Nt + s.L - 1) / s.L;
   s.W = (s.S + s.UPW - 1) / s.UPW;
@@ -60,7 +59,7 @@ static const BlksegShape& blkseg_shape(const qoc_ctx* c) {
     const int rb8 = std::min(8, rbmax);
     if (blkseg_lds(c->N, c->m, c->nu, c->blk_nb, c->nblk, c->Nt, s.S, s.W, rb8, pen) <= BLKSEG_LDS_MAX) s.RB = rb8;
   }
-  if (const char* e = getenv("QOC_BLKSEG_RB")) s.RB = std::max(1, std::min(atoi(e), rbmax));
+  if (env_set("QOC_BLKSEG_RB")) s.RB = std::max(1, std::min(env_int("QOC_BLKSEG_RB", 0), rbmax));
   s.lds = blkseg_lds(c->N, c->m, c->nu, c->blk_nb, c->nblk, c->Nt, s.S, s.W, s.RB, pen);
   std::copy(key, key + 8, c->seg_key);
   return s;
@@ -76,17 +75,10 @@ bool blkseg_ok(const qoc_ctx* c, int order) {
   if (!blku_on(c) || (c->blk_nb != 2 && c->blk_nb != 3) || !c->skew_exact || c->nblk > 32) return false;
   const bool exact = order == QOC_DUKDP_EXACT;
   if ((!exact && (order < 1 || order > BLK_ORDMAX)) || c->src_on) return false;
-  if (exact) {
-    const char* xe = getenv("QOC_BLKSEG_EXACT");
-    if (xe && !std::strcmp(xe, "0")) return false;
-  }
+  if (exact && env_is("QOC_BLKSEG_EXACT", "0")) return false;
   if (c->cost_kind != QOC_COST_TRACE && c->cost_kind != QOC_COST_ZCAL) return false;
-  const char* env = getenv("QOC_BLKSEG");
-  if (env && !std::strcmp(env, "0")) return false;
-  if (c->mu != 0.0) {
-    const char* pe = getenv("QOC_BLKSEG_PEN");
-    if ((pe && !std::strcmp(pe, "0")) || c->m > 32) return false;  // (the column mask has 32 bits)
-  }
+  if (env_is("QOC_BLKSEG", "0")) return false;
+  if (c->mu != 0.0 && (env_is("QOC_BLKSEG_PEN", "0") || c->m > 32)) return false;  // (the column mask has 32 bits)
   return blkseg_shape(c).lds <= BLKSEG_LDS_MAX;
 }
 
@@ -243,9 +235,7 @@ int blkseg_eval(qoc_ctx* c, int order, const double* d_u, double* d_J, double* d
 // and G at every segment's end, x_k rebuilt on demand.  Applies where the fused eval does (any order: the forward half
 // has none) unless QOC_BLKSEG_SPLIT=0.
 bool blkseg_split_ok(const qoc_ctx* c) {
-  const char* env = getenv("QOC_BLKSEG_SPLIT");
-  if (env && !std::strcmp(env, "0")) return false;
-  return blkseg_ok(c, 3);
+  return !env_is("QOC_BLKSEG_SPLIT", "0") && blkseg_ok(c, 3);
 }
 
 int blkseg_forward(qoc_ctx* c, const double* d_u, double* d_J) {

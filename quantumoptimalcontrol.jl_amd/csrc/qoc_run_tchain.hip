@@ -135,9 +135,8 @@ int tchain_prep(qoc_ctx* c) {
   // (profiles/bench_r05k_tb_*.json): the staged form writes fewer bytes but its prep is slower (0.41 vs 0.35 ms) and
   // the block chain after it ran 22.0 instead of 18.4 ms (writing full 64-entry rows, QOC_TCHEB_PW=64, did not
   // change that); with dead blocks skipped (blk_live) both give 15.1 ms.
-  const char* pk = getenv("QOC_TCHEB_PREP");
-  const char* pwe = getenv("QOC_TCHEB_PW");  // smallest coefficient row width the staged form writes
-  const int prep_kind = pk ? atoi(pk) : 0, prep_pw = pwe ? atoi(pwe) : 0;
+  const int prep_kind = env_int("QOC_TCHEB_PREP", 0);
+  const int prep_pw = env_int("QOC_TCHEB_PW", 0);  // smallest coefficient row width the staged form writes
   if (cheb && prep_kind == 0)
     hipLaunchKernelGGL(k_tchain_prep_cheb_strided, dim3(pb), dim3(256), 0, c->stream, c->nu, units,
                        (const double*)c->d_u, c->tprm, c->d_steps, c->d_tcoef, c->d_terms);
