@@ -439,10 +439,10 @@ template <int K = BLKSEG_KMAX>
 __device__ __forceinline__ void sk2_phase(double d0, double d1, double& ct, double& st) {
   constexpr BlksegTrig T = blkseg_trig();
   const double t = 0.5 * (d0 + d1), t2 = t * t;
-  ct = 0.0;
-  st = 0.0;
+  ct = T.c[K];  // (the Horner chains start at the top coefficient: fma(0, x, c) = c)
+  st = T.s[K];
 #pragma unroll
-  for (int k = K; k >= 0; --k) {
+  for (int k = K - 1; k >= 0; --k) {
     ct = fma(ct, t2, T.c[k]);
     st = fma(st, t2, T.s[k]);
   }
@@ -470,9 +470,9 @@ __device__ __forceinline__ void sk2_form(const Sk2 (&g)[3], double2 ph, double2 
   ah.q = fma(u.y, g[2].q, fma(u.x, g[1].q, g[0].q));
   const double a = 0.5 * (ah.d0 - ah.d1);
   const double w = fma(a, a, fma(ah.r, ah.r, ah.q * ah.q));
-  double cw = 0.0, sw = 0.0, s3 = 0.0, ct, st;
+  double cw = T.c[K], sw = T.s[K], s3 = EX ? T.d[K] : 0.0, ct, st;
 #pragma unroll
-  for (int k = K; k >= 0; --k) {
+  for (int k = K - 1; k >= 0; --k) {
     cw = fma(cw, w, T.c[k]);
     sw = fma(sw, w, T.s[k]);
     if constexpr (EX) s3 = fma(s3, w, T.d[k]);
@@ -513,9 +513,9 @@ __device__ __forceinline__ void sk2_form_v(const Sk2 (&g)[3], double2 u, double 
   ah.r = fma(u.y, g[2].r, fma(u.x, g[1].r, g[0].r));
   ah.q = fma(u.y, g[2].q, fma(u.x, g[1].q, g[0].q));
   const double w = fma(a0, a0, fma(ah.r, ah.r, ah.q * ah.q));
-  double cw = 0.0, sw = 0.0, s3 = 0.0;
+  double cw = T.c[K], sw = T.s[K], s3 = EX ? T.d[K] : 0.0;
 #pragma unroll
-  for (int k = K; k >= 0; --k) {
+  for (int k = K - 1; k >= 0; --k) {
     cw = fma(cw, w, T.c[k]);
     sw = fma(sw, w, T.s[k]);
     if constexpr (EX) s3 = fma(s3, w, T.d[k]);
@@ -610,7 +610,7 @@ __device__ __forceinline__ void sk2_contract(const Sk2& x, const Sk2& e1, const 
 //          Im m = (1 - x0²/2 - ω²/6) Im k + x0 Re k + (Re k0 - x0 Im k0 - Im d / 3) x
 // (the Pauli products (x.σ)(k.σ)(x.σ) = 2 (x.k) x.σ - ω² k.σ etc.; checked against the matrix recurrence in numpy).
 // ~73 flops instead of sk2_contract's 224 at order 3.  aj: the generators' Pauli vectors times 2 (pre-scaled so that
-// the K components below can stay doubled: 2 k0 = K00 + K11, ...).
+// the K components below can stay doubled: 2 k0 = K00 + K11, ...) times the trace's -1/2 (sk2_pauli2).
 // CX: X's diagonal is the same in every slice (zero-diagonal controls, zero control shifts): x0, x3 and x0² come
 // precomputed (x0c, x3c, x02c: the same values)
 template <int ORD, bool CX = false>
@@ -644,8 +644,8 @@ __device__ __forceinline__ void sk2_contract_pauli(const Sk2& x, const double (&
         m2 = fma(al1, k2i, fma(x0c, k2r, c * x2));
       }
     }
-    acc1 = -0.5 * fma(a1[2], m2, a1[1] * m1);
-    acc2 = -0.5 * fma(a2[2], m2, a2[1] * m1);
+    acc1 = fma(a1[2], m2, a1[1] * m1);
+    acc2 = fma(a2[2], m2, a2[1] * m1);
     return;
   }
   double m0, m1, m2, m3;  // 2 Im m
@@ -673,16 +673,17 @@ __device__ __forceinline__ void sk2_contract_pauli(const Sk2& x, const double (&
       m3 = fma(al1, k3i, fma(x0, k3r, c * x3));
     }
   }
-  // -2 a.Im m = -(a/2 ... ): aj holds 2 a, m holds 2 Im m, so the trace is -(aj.m) / 2
-  acc1 = -0.5 * fma(a1[3], m3, fma(a1[2], m2, fma(a1[1], m1, a1[0] * m0)));
-  acc2 = -0.5 * fma(a2[3], m3, fma(a2[2], m2, fma(a2[1], m1, a2[0] * m0)));
+  // -2 a.Im m: aj holds -(2 a) / 2 (sk2_pauli2), m holds 2 Im m, so the trace is aj.m
+  acc1 = fma(a1[3], m3, fma(a1[2], m2, fma(a1[1], m1, a1[0] * m0)));
+  acc2 = fma(a2[3], m3, fma(a2[2], m2, fma(a2[1], m1, a2[0] * m0)));
 }
-// doubled Pauli vector of an Sk2 generator block (sk2_contract_pauli's aj)
+// doubled Pauli vector of an Sk2 generator block times -1/2 (sk2_contract_pauli's aj: the trace's -1/2 folded in
+// where the vector is built, once per lane; a power of two, so every product and sum rounds as before)
 __device__ __forceinline__ void sk2_pauli2(const Sk2& e, double (&a)[4]) {
-  a[0] = e.d0 + e.d1;
-  a[1] = 2.0 * e.q;
-  a[2] = 2.0 * e.r;
-  a[3] = e.d0 - e.d1;
+  a[0] = -0.5 * (e.d0 + e.d1);
+  a[1] = -0.5 * (2.0 * e.q);
+  a[2] = -0.5 * (2.0 * e.r);
+  a[3] = -0.5 * (e.d0 - e.d1);
 }
 
 // The exact (Fréchet) traces in the same basis: the whole series M = Σ_{a,b >= 0} X^b K X^a / (a+b+1)! =
@@ -706,14 +707,14 @@ __device__ __forceinline__ void sk2_contract_exact(const Sk2& x, const double (&
   const double m1 = fma(zr, fma(sw, k1i, ci * x1), zi * fma(sw, k1r, cr * x1));
   const double m2 = fma(zr, fma(sw, k2i, ci * x2), zi * fma(sw, k2r, cr * x2));
   if constexpr (CX) {  // a1[0] = a1[3] = a2[0] = a2[3] = 0 exactly (sk2_contract_pauli): n0, m0 and m3 are not formed
-    acc1 = -0.5 * fma(a1[2], m2, a1[1] * m1);
-    acc2 = -0.5 * fma(a2[2], m2, a2[1] * m1);
+    acc1 = fma(a1[2], m2, a1[1] * m1);
+    acc2 = fma(a2[2], m2, a2[1] * m1);
   } else {
     const double n0r = fma(cw, k0r, -sw * di), n0i = fma(cw, k0i, sw * dr);
     const double m0 = fma(zr, n0i, zi * n0r);
     const double m3 = fma(zr, fma(sw, k3i, ci * x3), zi * fma(sw, k3r, cr * x3));
-    acc1 = -0.5 * fma(a1[3], m3, fma(a1[2], m2, fma(a1[1], m1, a1[0] * m0)));
-    acc2 = -0.5 * fma(a2[3], m3, fma(a2[2], m2, fma(a2[1], m1, a2[0] * m0)));
+    acc1 = fma(a1[3], m3, fma(a1[2], m2, fma(a1[1], m1, a1[0] * m0)));
+    acc2 = fma(a2[3], m3, fma(a2[2], m2, fma(a2[1], m1, a2[0] * m0)));
   }
 }
 
@@ -830,17 +831,23 @@ __device__ __forceinline__ void seg_turn(int grp, int ngrp, int jj) {
 }
 // SIMD partners by progress (QOC_PROBE builds: g_seg_turnmode 1): each wave posts its step count in LDS and runs the
 // next step at the higher issue priority when its partner (w ^ 4) is ahead (ties: the younger wave, which loses the
-// arbitration otherwise).  The partner's count is read one step early, so the LDS latency hides behind the step.
+// arbitration otherwise).  The partner's count is read at the end of a step for the next one.  DEFER: it stays in the
+// vector register it was loaded into until the next step makes it uniform, so that the read's latency hides behind
+// the step; otherwise the readfirstlane follows the read and waits for it at once (an LDS round trip per step).  The
+// deferred form costs one vector register over the loops: the instances that have none to give (blocks of 3 rows at
+// 256 VGPRs with scratch, the forward half) keep the other.
+template <bool DEFER>
 struct SegProg {
   int* prog;
-  int partner, other;
+  int partner, other;  // other: the partner's count (DEFER: as loaded, uniform in value but not yet scalar)
   bool on, young;
   __device__ __forceinline__ void step(int t) {
     if (!on) return;
-    if (other > t || (other == t && young)) __builtin_amdgcn_s_setprio(1);
+    const int o = DEFER ? __builtin_amdgcn_readfirstlane(other) : other;
+    if (o > t || (o == t && young)) __builtin_amdgcn_s_setprio(1);
     else __builtin_amdgcn_s_setprio(0);
     prog[threadIdx.x >> 6] = t;
-    other = __builtin_amdgcn_readfirstlane(prog[partner]);
+    other = DEFER ? prog[partner] : __builtin_amdgcn_readfirstlane(prog[partner]);
   }
 };
 
@@ -1104,7 +1111,7 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
   // SIMD partners (w, w + 4) alternate the issue priority (seg_turn); QOC_PROBE builds: g_seg_noturn turns it off
   const int grp = __builtin_amdgcn_readfirstlane(w >> 2), ngrp = (W + 3) >> 2;
   const bool turns = ngrp > 1 && SEG_TURNS && SEG_TURNMODE == 0;
-  SegProg sprog;
+  SegProg<NB == 2 && MODE != BLKSEG_FWD> sprog;
   sprog.prog = reinterpret_cast<int*>(red + 24);
   sprog.partner = __builtin_amdgcn_readfirstlane(w ^ 4);
   sprog.on = ngrp > 1 && SEG_TURNS && SEG_TURNMODE == 1 && sprog.partner < W;
@@ -1162,6 +1169,9 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
       }
     }
   };
+  // the records of the lane's segment: the no-select steps address them from a per-lane base (one address
+  // instruction per read; the shared base plus kb took a scalar that the loops had to fetch back from a spill)
+  const double* const reck = rec + 4 * (size_t)kb;
   auto p1_fast = [&](int jj, auto SEL_, auto K_, auto ZD_) {
     constexpr bool SEL = decltype(SEL_)::value;
     constexpr int KS = decltype(K_)::value;
@@ -1174,7 +1184,7 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
       for (int v = 0; v < 2; ++v) {
         const int k = kb + jj + v;
         act[v] = !SEL || (sact && jj + v < L && k < ke);
-        const double* r = rec + 4 * (size_t)(act[v] ? k : 0);
+        const double* r = SEL ? rec + 4 * (size_t)(act[v] ? k : 0) : reck + 4 * (size_t)(jj + v);
         Sk2 ah;
         sk2_form_v<KS>(gk, *reinterpret_cast<const double2*>(r + 2), za0, ah, vv[v]);
       }
@@ -1199,7 +1209,7 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
       for (int v = 0; v < 2; ++v) {
         const int k = kb + jj + v;
         act[v] = !SEL || (sact && jj + v < L && k < ke);
-        const double* r = rec + 4 * (size_t)(act[v] ? k : 0);
+        const double* r = SEL ? rec + 4 * (size_t)(act[v] ? k : 0) : reck + 4 * (size_t)(jj + v);
         Sk2 ah;
         sk2_form<KS>(gk, *reinterpret_cast<const double2*>(r), *reinterpret_cast<const double2*>(r + 2), ah, ur[v],
                      ui[v]);
@@ -1221,11 +1231,18 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
     }  // NB == 2
   };
   auto loop1z = [&](auto K_, auto ZD_) {
-    for (int jj = 0; jj < L; jj += 2) {
+    // the pairs wholly below Lf in a loop of their own (no selects, and nothing of the select variant's to merge at
+    // the loop's head), then the tail with the selects (no iterations when Lf = L is even)
+    int jj = 0;
+    for (; jj + 1 < Lf; jj += 2) {
       if (turns) seg_turn(grp, ngrp, jj >> 1);
       sprog.step(jj >> 1);
-      if (jj + 1 < Lf) p1_fast(jj, std::false_type(), K_, ZD_);
-      else p1_fast(jj, std::true_type(), K_, ZD_);
+      p1_fast(jj, std::false_type(), K_, ZD_);
+    }
+    for (; jj < L; jj += 2) {
+      if (turns) seg_turn(grp, ngrp, jj >> 1);
+      sprog.step(jj >> 1);
+      p1_fast(jj, std::true_type(), K_, ZD_);
     }
     // ZD: the segment product without its phase z^(ke - kb), as a matrix for phase 2 (negations only); everything
     // there but x_N is invariant to the phase
@@ -1756,7 +1773,7 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
       wave_lds_sync();
     }
   };
-  double pa1[4] = {0, 0, 0, 0}, pa2[4] = {0, 0, 0, 0};  // the generators' (A_j = Ã_j + i m_j I) doubled Pauli vectors
+  double pa1[4] = {0, 0, 0, 0}, pa2[4] = {0, 0, 0, 0};  // the generators' (A_j = Ã_j + i m_j I) doubled Pauli vectors times -1/2
   // ZD: X's diagonal in every slice (Ã_0's plus i Im μ_0) and its Pauli components
   const double zxd0 = NB == 2 ? gk[0].d0 + sp.mui[0] : 0.0, zxd1 = NB == 2 ? gk[0].d1 + sp.mui[0] : 0.0;
   const double zx0 = 0.5 * (zxd0 + zxd1), zx3 = 0.5 * (zxd0 - zxd1), zx02 = zx0 * zx0;
@@ -1764,15 +1781,16 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
     sk2_pauli2(Sk2{gk[1].d0 + mu1i, gk[1].d1 + mu1i, gk[1].r, gk[1].q}, pa1);
     sk2_pauli2(Sk2{gk[2].d0 + mu2i, gk[2].d1 + mu2i, gk[2].r, gk[2].q}, pa2);
   }
-  auto p3_fast = [&](int jj, auto SEL_, auto K_, auto ZD_) {
+  // upre: the slice's controls where the caller has read them already (the no-select loop's read-ahead)
+  auto p3_fast = [&](int jj, auto SEL_, auto K_, auto ZD_, const double2* upre = nullptr) {
     constexpr bool SEL = decltype(SEL_)::value;
     constexpr int KS = decltype(K_)::value;
     constexpr bool ZD = decltype(ZD_)::value;
     if constexpr (NB == 2) {
       const int k = kb + jj;
       const bool act = !SEL || (sact && k < ke);
-      const double* r = rec + 4 * (size_t)(act ? k : 0);
-      const double2 u = *reinterpret_cast<const double2*>(r + 2);
+      const double* r = SEL ? rec + 4 * (size_t)(act ? k : 0) : reck + 4 * (size_t)jj;
+      const double2 u = upre ? *upre : *reinterpret_cast<const double2*>(r + 2);
       Sk2 ah;
       double ur[4], ui[4], ex[5];
       if constexpr (ZD) {  // V_k as a matrix (negations only) and Ĝ in Gr, Gi: the same K_k
@@ -1816,11 +1834,27 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
     }
   };
   auto loop3z = [&](auto K_, auto ZD_) {
-    for (int jj = L - 1; jj >= 0; --jj) {
+    // the steps at and above Lf first, with the selects (none when Lf = L), then the rest in a loop of their own
+    int jj = L - 1;
+    for (; jj >= Lf; --jj) {
       if (turns) seg_turn(grp, ngrp, jj);
       sprog.step(L + (L - 1 - jj));
-      if (jj < Lf) p3_fast(jj, std::false_type(), K_, ZD_);
-      else p3_fast(jj, std::true_type(), K_, ZD_);
+      p3_fast(jj, std::true_type(), K_, ZD_);
+    }
+    // ZD: the slice's controls are read one step ahead (the next step's while this one runs: the read's latency
+    // stood at the head of every step), the last step reads its own again
+    constexpr bool PRE = decltype(ZD_)::value;
+    double2 un = make_double2(0.0, 0.0);
+    if (PRE && jj >= 0) un = *reinterpret_cast<const double2*>(reck + 4 * (size_t)jj + 2);
+    for (; jj >= 0; --jj) {
+      if (turns) seg_turn(grp, ngrp, jj);
+      sprog.step(L + (L - 1 - jj));
+      const double2 uc = un;
+      if constexpr (PRE) {
+        un = *reinterpret_cast<const double2*>(reck + 4 * (size_t)max(jj - 1, 0) + 2);
+        __builtin_amdgcn_sched_barrier(0);
+      }
+      p3_fast(jj, std::false_type(), K_, ZD_, PRE ? &uc : nullptr);
     }
   };
   auto loop3 = [&](auto K_) {
