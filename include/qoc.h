@@ -39,7 +39,11 @@ extern "C" {
  * the reference's definition; 3 in the Ipopt path); QOC_DUKDP_EXACT = exact Fréchet derivative of the
  * propagator (opt-in).  Where the segmented eval applies (invariant blocks of <= 3 rows:
  * cavity, zz) it is that kernel's exact contraction, the whole series of the trace form, closed form on blocks of
- * 2 rows; elsewhere, or with QOC_BLKSEG_EXACT=0, one 2N x 2N block exponential per slice and control. */
+ * 2 rows.  On invariant blocks of 5-16 rows with one control (the tunable bus) it is the derivative of the
+ * interpolating block propagators' own curve, dU/du = e^{mu(u)} sum_i T_i(xi) N_i, on the stored / interpolating
+ * propagators (fused and split call forms, penalty and co-state source, TRACE and ZCAL; QOC_BLKP_EXACT=0 off).
+ * Elsewhere (two controls on such blocks, a control range the interpolation cannot resolve, QOC_BLKP_INTERP=0,
+ * QOC_BLKP=0, QOC_COST_EXTERNAL), or with QOC_BLKSEG_EXACT=0, one 2N x 2N block exponential per slice and control. */
 #define QOC_DUKDP_EXACT 0
 
 #define QOC_COST_TRACE 0     /* J = 1-|tr(X'x)|^2/n^2            (src/penalty_fcns.jl:15-24) */
@@ -198,7 +202,8 @@ int qoc_propagate_envelope(qoc_ctx* ctx, int kind, const double* params, int np,
  * last backward ran (0 generic, 1 from the chains' captured products, 2 concurrent μ recurrence of qoc_eval_dev on
  * a second stream, 3 the same in one launch with the forward chain, 4 the block chains' concurrent eval, 5 the block
  * propagators' fused backward: λ kept on chip, the gradient contracted beside the chain; qoc_get_costates then
- * rebuilds λ on demand),
+ * rebuilds λ on demand, 6 the segmented block eval, 7 the stored / interpolating propagators of blocks of 5..16
+ * rows: order 3, and QOC_DUKDP_EXACT where their interpolation in u applies),
  * info[9] = 1 when the last forward chain wrote its captured products, info[10] = the Taylor-action chain kernels
  * (0 none / the fp32 VALU ones, 1 MFMA with the state in LDS, 2 MFMA with the state in registers: N <= 32, nu <= 2,
  * QOC_TCHAIN_ROT=0 keeps 1; 3 block chains: the generators split into invariant blocks of <= 4 rows, one VALU lane

@@ -1586,4 +1586,190 @@ __global__ __launch_bounds__(256, 2) void k_blkp_grad(const BlkpGradArgs a) {
   }
 }
 
+// ---- one control: the exact gradient from the interpolation's own curve (dUkdp_order = QOC_DUKDP_EXACT) ----
+// The slice propagators lie on U(u) = e^{μ(u)} Σ_i T_i(ξ) M_i, ξ = xa u + xb (k_blkp_int), so the Fréchet derivative
+// along A_1 is the derivative of that curve,
+//   dU/du = e^{μ(u)} Σ_i T_i(ξ) N_i,   N_i = μ_1 M_i + xa M'_i,
+// M' the coefficients of the differentiated series (M'_{i-1} = M'_{i+1} + 2 i M_i, M'_0 halved; the host forms N_i in
+// long double beside M_i, blkp_interp_coeffs): no block exponential, no squaring, no 2N x 2N matrix.
+//   dJ/du_k = Re[e^{μ(u_k)} Σ_{β, col} Σ_{r, c} conj(λ_{k+1}[r, col]) (Σ_i T_i(ξ_k) N_i)[r][c] x_k[c, col]]
+// The slices are independent: one wave takes BLKP_GX_UPW consecutive slices of one seed, so that each coefficient read
+// from the LDS serves them all; lane l holds entries 64 e + l of the layout the coefficients were uploaded in (the
+// propagator store positions blkp_upos, or SYM: the packed upper triangle of the symmetric propagators' derivative,
+// whose off-diagonal entries weigh both orderings).  Every (seed, slice) belongs to one wave, which sums its state
+// columns and this launch's blocks [beta0, beta0 + nb) (as many as their coefficients fit the LDS) in a fixed order:
+// no atomics, the same bits whatever the grid.  A later block group adds to the first one's dJdu (accum).  x_k and
+// λ_{k+1} come through two staging rows per wave: one gather per (slice, block row) lane, issued before the Chebyshev
+// sums so that the HBM latency passes under them, then every entry's (r, c) pair from the LDS.
+struct BlkpGxArgs {
+  int N, m, Nt, B, nwb;
+  int E;                     // the largest degree of N (the coefficients' stride E + 1)
+  int beta0, nb;             // this launch's blocks
+  int Eb[8];                 // each block's own degree
+  const int* wrow;           // nwb x 16 rows of the live wave blocks
+  const double* u;           // B x Nt
+  double xa, xb;             // ξ = xa u + xb
+  double mur[2], mui[2];     // μ(u) = μ_0 + u μ_1
+  int skew;                  // imaginary shifts
+  const double2* Nc;         // [β][i][p] (p = blkp_upos(r, c)), SYM: [i][slot] of block 0's nl live rows
+  int nl;
+  const cx<double>* X;       // B x (Nt+1) x N x m states
+  const cx<double>* L;       // μ_k (LAM: λ_k)
+  const cx<double>* coef;    // B x 2m λ_N coefficients
+  double* dJdu;              // B x Nt
+  int accum;                 // add to dJdu (the block groups after the first)
+  const int* stale;          // as k_blkp_grad's
+  cx<double>* coef_out;
+};
+constexpr int BLKP_GX_UPW = 4, BLKP_GX_WG = 512;
+static_assert(BLKP_GX_UPW * 16 == 64, "one staging lane per (slice, block row)");
+// LDS: the launch's coefficients | per wave: x_k and λ_{k+1} on the block's 16 rows for the wave's UPW slices
+__host__ __device__ inline size_t blkp_gx_lds(int nb, int E, bool sym, int waves) {
+  return ((size_t)nb * (E + 1) * (sym ? 128 : 256) + (size_t)waves * 128) * sizeof(double2);
+}
+
+// blockDim.x = 64 x waves <= BLKP_GX_WG (fewer waves where the coefficients leave less LDS for their staging rows)
+template <bool LAM, bool SYM>
+__global__ __launch_bounds__(BLKP_GX_WG) void k_blkp_grad_exact(const BlkpGxArgs a) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  if (a.stale && *a.stale != 0) return;
+  constexpr int UPW = BLKP_GX_UPW, NE = SYM ? 2 : 4, ES = SYM ? 128 : 256;
+  double2* Ns = reinterpret_cast<double2*>(smem);
+  // (the wave index as a scalar: the seed, the slices and the state / co-state base addresses then stay in SGPRs)
+  const int tid = threadIdx.x, l = tid & 63, w = __builtin_amdgcn_readfirstlane(tid >> 6), WV = (int)(blockDim.x >> 6);
+  const int N = a.N, m = a.m, Nt = a.Nt, E = a.E, nb = a.nb;
+  if (a.coef_out && blockIdx.x == 0)
+    for (int e = tid; e < a.B * 2 * m; e += blockDim.x) a.coef_out[e] = a.coef[e];
+  for (int e = tid; e < nb * (E + 1) * ES; e += blockDim.x) Ns[e] = a.Nc[(size_t)a.beta0 * (E + 1) * ES + e];
+  __syncthreads();
+  double2* const xs = Ns + (size_t)nb * (E + 1) * ES + (size_t)w * 128;  // [t][position] x_k, then the same of λ_{k+1}
+  double2* const ls = xs + 64;
+  // the positions (r, c) within the wave block of this lane's entries (a slot past the triangle: zero coefficients)
+  int pa[NE], pc[NE];
+  bool off[NE];
+#pragma unroll
+  for (int e = 0; e < NE; ++e) {
+    if (SYM) {
+      int s = 64 * e + l, p = 0;
+      while (p < a.nl && s >= a.nl - p) s -= a.nl - p++;
+      pa[e] = p < a.nl ? p : 0;
+      pc[e] = p < a.nl ? p + s : 0;
+      off[e] = p < a.nl && s != 0;
+    } else {
+      pc[e] = 4 * ((l >> 4) & 3) + e;
+      pa[e] = (l & 15) ^ pc[e];
+      off[e] = false;
+    }
+  }
+  const int st = l >> 4, sp = l & 15;  // staging: lane l fetches row position sp of the wave's slice st
+  const size_t Nm = (size_t)N * m;
+  const int G = (Nt + UPW - 1) / UPW;
+  const long long items = (long long)a.B * G;
+  for (long long it = (long long)blockIdx.x * WV + w; it < items; it += (long long)gridDim.x * WV) {
+    const int b = (int)(it / G), k0 = (int)(it - (long long)b * G) * UPW;
+    double xi[UPW], sr[UPW], si[UPW];
+#pragma unroll
+    for (int t = 0; t < UPW; ++t) {
+      xi[t] = fma(a.xa, a.u[(size_t)b * Nt + min(k0 + t, Nt - 1)], a.xb);
+      sr[t] = si[t] = 0.0;
+    }
+    const size_t sbase = ((size_t)b * (Nt + 1) + min(k0 + st, Nt - 1)) * Nm;  // x_k of the staging lane's slice
+    for (int bl = 0; bl < nb; ++bl) {
+      const int beta = a.beta0 + bl;
+      const int srow = a.wrow[16 * beta + sp];
+      // x_k[row, c] and μ_{k+1}[row, c] (zero on a padding row): one gather per column, the first one in flight under
+      // the Chebyshev sums
+      auto fetch = [&](int c, cx<double>& xv, cx<double>& lv) __attribute__((always_inline)) {
+        xv = lv = cx<double>{0.0, 0.0};
+        if (srow >= 0) {
+          xv = a.X[sbase + (size_t)c * N + srow];
+          lv = a.L[sbase + Nm + (size_t)c * N + srow];
+        }
+      };
+      cx<double> xv, lv;
+      fetch(0, xv, lv);
+      // Σ_i T_i(ξ_t) N_i on this lane's entries
+      double ar[UPW][NE], ai[UPW][NE], tm[UPW], tc[UPW];
+#pragma unroll
+      for (int t = 0; t < UPW; ++t) {
+        tm[t] = tc[t] = 1.0;
+#pragma unroll
+        for (int e = 0; e < NE; ++e) ar[t][e] = ai[t][e] = 0.0;
+      }
+      const double2* Nb = Ns + (size_t)bl * (E + 1) * ES + l;
+      int Eq = 0;  // (a.Eb[beta] without a dynamic index into the kernel arguments)
+#pragma unroll
+      for (int j = 0; j < 8; ++j) Eq = j == beta ? a.Eb[j] : Eq;
+#pragma unroll 2
+      for (int i = 0; i <= Eq; ++i) {
+        double2 nv[NE];
+#pragma unroll
+        for (int e = 0; e < NE; ++e) nv[e] = Nb[(size_t)i * ES + 64 * e];
+#pragma unroll
+        for (int t = 0; t < UPW; ++t) {
+#pragma unroll
+          for (int e = 0; e < NE; ++e) {
+            ar[t][e] = fma(tc[t], nv[e].x, ar[t][e]);
+            ai[t][e] = fma(tc[t], nv[e].y, ai[t][e]);
+          }
+          const double tn = i == 0 ? xi[t] : fma(2.0 * xi[t], tc[t], -tm[t]);  // T_{i+1} = 2 ξ T_i - T_{i-1}
+          tm[t] = tc[t];
+          tc[t] = tn;
+        }
+      }
+      // Σ_col conj(λ_{k+1}[r, col]) x_k[c, col] against them, the rows through the wave's staging rows
+      for (int c = 0; c < m; ++c) {
+        if (c > 0) fetch(c, xv, lv);
+        if (!LAM) {
+          const cx<double> cf = a.coef[(size_t)b * 2 * m + c];
+          lv = cx<double>{cf.r * lv.r - cf.i * lv.i, cf.r * lv.i + cf.i * lv.r};
+        }
+        blkp_wave_sync();  // (the reads of the column before)
+        xs[l] = make_double2(xv.r, xv.i);
+        ls[l] = make_double2(lv.r, lv.i);
+        blkp_wave_sync();
+#pragma unroll
+        for (int t = 0; t < UPW; ++t) {
+#pragma unroll
+          for (int e = 0; e < NE; ++e) {
+            const double2 la = ls[16 * t + pa[e]], xc = xs[16 * t + pc[e]];
+            double wr_ = fma(la.x, xc.x, la.y * xc.y), wi_ = fma(la.x, xc.y, -(la.y * xc.x));
+            if (SYM && off[e]) {  // dU[c][r] = dU[r][c]
+              const double2 lc = ls[16 * t + pc[e]], xr = xs[16 * t + pa[e]];
+              wr_ += fma(lc.x, xr.x, lc.y * xr.y);
+              wi_ += fma(lc.x, xr.y, -(lc.y * xr.x));
+            }
+            sr[t] += fma(wr_, ar[t][e], -(wi_ * ai[t][e]));
+            si[t] += fma(wr_, ai[t][e], wi_ * ar[t][e]);
+          }
+        }
+      }
+    }
+#pragma unroll
+    for (int t = 0; t < UPW; ++t)
+      for (int o = 32; o > 0; o >>= 1) {
+        sr[t] += __shfl_xor(sr[t], o);
+        si[t] += __shfl_xor(si[t], o);
+      }
+    // lane t: slice k0 + t
+    double vr = sr[0], vi = si[0];
+#pragma unroll
+    for (int t = 1; t < UPW; ++t)
+      if (l == t) {
+        vr = sr[t];
+        vi = si[t];
+      }
+    if (l < UPW && k0 + l < Nt) {
+      const size_t o = (size_t)b * Nt + k0 + l;
+      const double uu = a.u[o];
+      const double mr = fma(uu, a.mur[1], a.mur[0]), mi = fma(uu, a.mui[1], a.mui[0]);
+      const double em = a.skew ? 1.0 : exp(mr);
+      double sn, cn;
+      sincos(mi, &sn, &cn);
+      const double v = em * fma(cn, vr, -(sn * vi));
+      a.dJdu[o] = a.accum ? a.dJdu[o] + v : v;
+    }
+  }
+}
+
 }  // namespace qoc

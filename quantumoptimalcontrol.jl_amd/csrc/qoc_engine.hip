@@ -342,12 +342,20 @@ int forward(qoc_ctx* c, const double* d_src = nullptr, double* d_J = nullptr) {
     HIPCHK(c, hipMemcpyAsync(d_J, c->d_J, c->B * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   return r;
 }
+int wait_stale_check(qoc_ctx* c);
 // stale: a device stale-u flag the segmented backward checks itself (queue_stale_check), or nullptr
 int backward(qoc_ctx* c, int order, double* d_dJdu, const int* stale = nullptr) {
   // the segmented forward left G at every segment's end: the backward half only (x_k never formed); the stored block
   // propagators: the μ recurrence and the gradient on them
   if (c->fwd_kind == 1 && blkseg_ok(c, order)) return blkseg_backward(c, order, d_dJdu, stale);
-  if (blkp_backward_ok(c, order)) return blkp_backward(c, d_dJdu, stale);
+  if (blkp_backward_ok(c, order)) {
+    const int r = blkp_backward(c, order, d_dJdu, stale);
+    if (r != 1) return r;
+    // 1: an exact backward whose (sourced) block layout has no converged interpolation, nothing launched: the dense
+    // path below, which reads no device flag, so after the stale check
+    if (stale)
+      if (const int w = wait_stale_check(c)) return w;
+  }
   if (c->cost_kind == QOC_COST_EXTERNAL || c->src_on) c->dead_dirty = true;  // λ may be nonzero on dead rows
   if (c->X_lazy) {  // after a segmented eval: the backward paths read x_k
     const int r = blku_states(c);
@@ -1013,14 +1021,16 @@ int qoc_eval_dev(qoc_ctx* c, const double* d_u, int order, double* d_J, double* 
     r = blk_concurrent_ok(c, order)  ? blk_eval_concurrent(c, order, d_dJdu ? d_dJdu : c->d_dJdu)
         : c->prec == QOC_FP64 ? tchain_eval_concurrent<double>(c, d_dJdu ? d_dJdu : c->d_dJdu)
                               : tchain_eval_concurrent<float>(c, d_dJdu ? d_dJdu : c->d_dJdu);
-    if (r) return r;
-    c->props_since_reset++;
-    if (d_J && d_J != c->d_J)
-      HIPCHK(c, hipMemcpyAsync(d_J, c->d_J, c->B * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    c->have_prop = true;
-    c->h_u.clear();
-    c->h_coef.clear();
-    return QOC_OK;
+    if (r != 1) {  // (1: an exact eval off the interpolating block propagators, nothing launched: the calls below)
+      if (r) return r;
+      c->props_since_reset++;
+      if (d_J && d_J != c->d_J)
+        HIPCHK(c, hipMemcpyAsync(d_J, c->d_J, c->B * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+      c->have_prop = true;
+      c->h_u.clear();
+      c->h_coef.clear();
+      return QOC_OK;
+    }
   }
   int r = qoc_propagate_dev(c, d_u, d_J);
   if (r) return r;

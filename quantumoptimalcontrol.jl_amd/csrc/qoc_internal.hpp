@@ -180,6 +180,12 @@ struct qoc_ctx {
   bool int_sym = false;              // complex-symmetric generators on one live wave block: d_blkp_M also holds its
   int int_nl = 0;                    // packed upper triangle of int_nl live rows, from element int_nfull on
   size_t int_nfull = 0;
+  // the exact gradient's coefficients N_i (dU/du on the same curve, k_blkp_grad_exact) beside them, recomputed with
+  // them: degree int_E (per block int_Eb), the full layout from element int_noff, the triangle from int_nsoff
+  int int_E = 0;
+  std::vector<int> int_Eb;
+  size_t int_noff = 0, int_nsoff = 0;
+  bool blkp_fwd_interp = false;      // blkp_forward's propagators were interpolated (the exact backward needs N_i)
   bool int_failed = false;           // [int_fail_lo, int_fail_hi] did not converge (a wider range will not either)
   double int_fail_lo = 0.0, int_fail_hi = 0.0;
   double* d_minmax = nullptr;        // k_minmax partials (256 blocks x 2)
@@ -416,12 +422,14 @@ int blk_zero_dead(qoc_ctx* c, std::initializer_list<void*> bufs);
 // ---- qoc_run_blkp.hip ----
 int blkp_pen_mode(const qoc_ctx* c);  // a penalty / co-state source: 0 none in effect, 1 the PEN chains, 2 Chebyshev
 bool blkp_fits_nwb(const qoc_ctx* c, int nwb);
-int blkp_eval_concurrent(qoc_ctx* c, double* d_dJdu, const BlkArgs& bk);  // 1: the propagators do not fit in HBM
+bool blkp_exact_on(const qoc_ctx* c);  // QOC_DUKDP_EXACT may stay on them (one control, the interpolation not switched off)
+// 1 (nothing launched): the propagators do not fit in HBM, or exact without a converged interpolation
+int blkp_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu, const BlkArgs& bk);
 // the reference's split call form for blocks of 5..16 rows on stored propagators: propagate = formation + forward
 // chain (1: not applicable), grape_sensitivity = the μ recurrence + the order-3 gradient
 int blkp_forward(qoc_ctx* c);
 bool blkp_backward_ok(const qoc_ctx* c, int order);
-int blkp_backward(qoc_ctx* c, double* d_dJdu, const int* stale);
+int blkp_backward(qoc_ctx* c, int order, double* d_dJdu, const int* stale);  // 1: exact, see blkp_eval_concurrent
 
 // ---- qoc_run_blku.hip ----
 int blku_forward(qoc_ctx* c);

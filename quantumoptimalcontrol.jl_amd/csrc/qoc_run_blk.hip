@@ -378,16 +378,19 @@ int blk_backward(qoc_ctx* c, int order, double* d_dJdu) {
 // (λ_k = coef ⊙ μ_k, src/penalty_fcns.jl:19-22, 35-40) in one launch, then the gradient with the coefficients.  (With a
 // penalty or a source λ_k needs x_k: the two directions run in sequence, qoc_propagate_dev then the backward.)
 bool blk_concurrent_ok(const qoc_ctx* c, int order) {
-  // MFMA block waves: the contraction from the chains' captures (k_grad_rr_c, order 3)
-  if (blk_big(c) && !(order == 3 && tchain_cap_ok(c))) return false;
+  // MFMA block waves: the contraction from the chains' captures (k_grad_rr_c, order 3); the exact gradient on the
+  // interpolating propagators of blocks of 5..16 rows (blkp_exact_on: blk_eval_concurrent may still return 1)
+  const bool exact = order == QOC_DUKDP_EXACT && blk_big(c) && blkp_exact_on(c);
+  if (blk_big(c) && !(order == 3 && tchain_cap_ok(c)) && !exact) return false;
   // (blocks of 5..16 rows: a penalty without a penalised entry in a live block is no penalty, blkp_pen_mode)
-  return blk_active(c) && c->concurrent && order >= 1 && order <= BLK_ORDMAX &&
+  return blk_active(c) && c->concurrent && ((order >= 1 && order <= BLK_ORDMAX) || exact) &&
          (c->cost_kind == QOC_COST_TRACE || c->cost_kind == QOC_COST_ZCAL) &&
          ((c->mu == 0.0 && !c->src_on) || (blkp_on(c) && blkp_pen_mode(c) == 0));
 }
 
 // The router of the concurrent eval: the block propagators (blocks of <= 4 rows), the stored propagators (5..16 rows),
-// else the Chebyshev block chains, whose eval this is
+// else the Chebyshev block chains, whose eval this is.  Returns 1, with nothing launched, for an exact eval whose
+// interpolation does not apply (a control range the series cannot resolve): the caller runs propagate + backward
 int blk_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu) {
   if (blku_on(c)) return blku_eval_concurrent(c, order, d_dJdu);
   int r;
@@ -396,10 +399,11 @@ int blk_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu) {
     BlkArgs bk = blk_args(c);
     if ((r = blk_live(c, bk))) return r;
     if (blkp_fits_nwb(c, bk.nwb)) {
-      r = blkp_eval_concurrent(c, d_dJdu, bk);
+      r = blkp_eval_concurrent(c, order, d_dJdu, bk);
       if (r != 1) return r;  // 1: the propagators do not fit in HBM: the Chebyshev block chains below
     }
   }
+  if (order == QOC_DUKDP_EXACT) return 1;
   if ((r = blk_big(c) ? ensure_pws(c) : QOC_OK)) return r;
   if ((r = tchain_prep(c))) return r;
   TChainArgs gf = tchain_args(c);

@@ -350,6 +350,44 @@ static int blkp_interp_coeffs(qoc_ctx* c, const std::vector<int>& wrow, double l
     D = std::max(D, d);
   }
   if (blkp_int_lds(1, D) > (size_t)150 * 1024) return 1;  // one block's coefficients per launch at least
+  // The exact gradient's coefficients (qoc_blkp.hpp k_blkp_grad_exact): dU/du = e^{μ(u)} Σ_i T_i(ξ) N_i with
+  // N_i = μ_1 M_i + xa M'_i, xa = dξ/du = 1 / half, and M' the differentiated series: M'_{i-1} = M'_{i+1} + 2 i M_i
+  // downwards, M'_0 halved.  The series differentiated is the one the chains apply, i <= Db: the coefficients past it
+  // are the long-double transform's floor (~2e-18), which the recurrence's factors 2 i xa would raise to ~1e-15 in
+  // every N_i, above the 2^-56 the tail rule asks for, while what they still carry of the curve is below it.  Each
+  // block's own degree Eb <= Db by the same tail rule; symmetrised M_i give symmetric N_i entry by entry.
+  std::vector<std::vector<LD>> Gr((size_t)nwb * NI, std::vector<LD>(256, 0)), Gi = Gr;
+  std::vector<int> Eb(nwb);
+  int E = 0;
+  {
+    const LD m1r = c->tprm.mur[1], m1i = c->tprm.mui[1];
+    for (int b = 0; b < nwb; ++b) {
+      const int d = Db[b];
+      for (int e = 0; e < 256; ++e) {
+        LD pr[NI + 2] = {0}, pi2[NI + 2] = {0};
+        for (int i = d; i >= 1; --i) {
+          pr[i - 1] = pr[i + 1] + 2 * i * Mr[(size_t)b * NI + i][e];
+          pi2[i - 1] = pi2[i + 1] + 2 * i * Mi[(size_t)b * NI + i][e];
+        }
+        pr[0] /= 2;
+        pi2[0] /= 2;
+        for (int i = 0; i <= d; ++i) {
+          const LD mr = Mr[(size_t)b * NI + i][e], mi = Mi[(size_t)b * NI + i][e];
+          Gr[(size_t)b * NI + i][e] = m1r * mr - m1i * mi + pr[i] / half;
+          Gi[(size_t)b * NI + i][e] = m1r * mi + m1i * mr + pi2[i] / half;
+        }
+      }
+      int dd = d;
+      auto small = [&](int i) {
+        for (int e = 0; e < 256; ++e)
+          if (std::max(std::fabs(Gr[(size_t)b * NI + i][e]), std::fabs(Gi[(size_t)b * NI + i][e])) > tol) return false;
+        return true;
+      };
+      while (dd > 0 && small(dd)) --dd;
+      Eb[b] = dd;
+      E = std::max(E, dd);
+    }
+  }
   std::vector<double2> h((size_t)nwb * (D + 1) * 256);
   for (int b = 0; b < nwb; ++b)
     for (int i = 0; i <= D; ++i)
@@ -367,6 +405,23 @@ static int blkp_interp_coeffs(qoc_ctx* c, const std::vector<int>& wrow, double l
           h[nfull + (size_t)i * 128 + blkp_sym_slot(a, b2, nl)] =
               make_double2((double)Mr[i][a * 16 + b2], (double)Mi[i][a * 16 + b2]);
   }
+  // N_i after them in the same two layouts: [β][i][p] with stride E + 1, then (sym) block 0's packed upper triangle
+  const size_t noff = h.size();
+  h.resize(noff + (size_t)nwb * (E + 1) * 256 + (sym ? (size_t)(E + 1) * 128 : 0), make_double2(0.0, 0.0));
+  for (int b = 0; b < nwb; ++b)
+    for (int i = 0; i <= E; ++i)
+      for (int p = 0; p < 256; ++p) {
+        const int col = 4 * ((p >> 4) & 3) + (p >> 6), row = (p & 15) ^ col, ent = row * 16 + col;
+        h[noff + ((size_t)b * (E + 1) + i) * 256 + p] =
+            make_double2((double)Gr[(size_t)b * NI + i][ent], (double)Gi[(size_t)b * NI + i][ent]);
+      }
+  const size_t nsoff = noff + (size_t)nwb * (E + 1) * 256;
+  if (sym)
+    for (int i = 0; i <= E; ++i)
+      for (int a = 0; a < nl; ++a)
+        for (int b2 = a; b2 < nl; ++b2)
+          h[nsoff + (size_t)i * 128 + blkp_sym_slot(a, b2, nl)] =
+              make_double2((double)Gr[i][a * 16 + b2], (double)Gi[i][a * 16 + b2]);
   const size_t bytes = h.size() * sizeof(double2);
   if (c->blkp_M_bytes < bytes) {
     if (c->d_blkp_M) {
@@ -384,6 +439,10 @@ static int blkp_interp_coeffs(qoc_ctx* c, const std::vector<int>& wrow, double l
   c->int_sym = sym;
   c->int_nl = nl;
   c->int_nfull = nfull;
+  c->int_E = E;
+  c->int_Eb = Eb;
+  c->int_noff = noff;
+  c->int_nsoff = nsoff;
   c->int_lo = lo;
   c->int_hi = hi;
   c->int_wrow = wrow;
@@ -626,6 +685,71 @@ static int blkp_launch_grad(qoc_ctx* c, const BlkArgs& bk, double* d_dJdu, const
   HIPCHK(c, hipGetLastError());
   return QOC_OK;
 }
+// The exact gradient (QOC_DUKDP_EXACT) stays on these propagators where their interpolation applies: one control,
+// QOC_BLKP_INTERP != 0 (and a converged series: known once the coefficients of the batch's range are formed);
+// QOC_BLKP_EXACT=0 leaves it to the block exponential of the dense path
+bool blkp_exact_on(const qoc_ctx* c) {
+  return blkp_on(c) && c->nu == 1 && env_int("QOC_BLKP_INTERP", 1) != 0 && env_int("QOC_BLKP_EXACT", 1) != 0;
+}
+// the exact gradient from x_k, μ_{k+1} (lam: λ_{k+1}) and the cached derivative coefficients N_i of bk's layout
+// (c->int_*: blkp_interp_coeffs), in place of blkp_launch_grad
+static int blkp_launch_grad_exact(qoc_ctx* c, const BlkArgs& bk, double* d_dJdu, const int* stale, cx<double>* coef_out,
+                                  bool lam = false) {
+  const std::vector<int>& wrow = bk.wrow == c->d_wrow_live ? c->h_wrow_live : c->h_wrow;
+  if (!(c->int_ok && wrow == c->int_wrow && (int)c->int_Eb.size() == bk.nwb && bk.nwb <= 8))
+    return fail(c, QOC_ERR_STATE, "exact block gradient: no derivative coefficients for this block layout");
+  BlkpGxArgs ga{};
+  ga.N = c->N;
+  ga.m = c->m;
+  ga.Nt = c->Nt;
+  ga.B = c->B;
+  ga.nwb = bk.nwb;
+  ga.E = c->int_E;
+  for (int b = 0; b < bk.nwb; ++b) ga.Eb[b] = c->int_Eb[b];
+  ga.wrow = bk.wrow;
+  ga.u = c->d_u;
+  ga.xa = 2.0 / (c->int_hi - c->int_lo);
+  ga.xb = -(c->int_hi + c->int_lo) / (c->int_hi - c->int_lo);
+  for (int j = 0; j < 2; ++j) {
+    ga.mur[j] = c->tprm.mur[j];
+    ga.mui[j] = c->tprm.mui[j];
+  }
+  ga.skew = c->skew_exact && c->tprm.mur[0] == 0.0 && c->tprm.mur[1] == 0.0;
+  // complex-symmetric generators: the upper triangle alone (QOC_BLKP_ISYM=0: every entry)
+  const bool sym = c->int_sym && bk.nwb == 1 && env_int("QOC_BLKP_ISYM", 1) != 0;
+  ga.Nc = c->d_blkp_M + (sym ? c->int_nsoff : c->int_noff);
+  ga.nl = sym ? c->int_nl : 0;
+  ga.X = (const cx<double>*)c->d_X;
+  ga.L = (const cx<double>*)c->d_L;
+  ga.coef = c->d_coef;
+  ga.dJdu = d_dJdu;
+  ga.stale = stale;
+  auto gk = sym ? (lam ? k_blkp_grad_exact<true, true> : k_blkp_grad_exact<false, true>)
+                : (lam ? k_blkp_grad_exact<true, false> : k_blkp_grad_exact<false, false>);
+  // 8 waves per workgroup, 4 where one block's coefficients leave no room for 8 waves' staging rows (E <= D: 148 KB at
+  // the most); as many blocks per launch as fit the LDS beside them
+  const int waves = blkp_gx_lds(1, ga.E, sym, BLKP_GX_WG / 64) <= (size_t)160 * 1024 ? BLKP_GX_WG / 64 : 4;
+  const size_t room = (size_t)160 * 1024 - blkp_gx_lds(0, ga.E, sym, waves);
+  const int per = std::max(1, std::min(bk.nwb, (int)(room / blkp_gx_lds(1, ga.E, sym, 0))));
+  const long long items = (long long)c->B * ((c->Nt + BLKP_GX_UPW - 1) / BLKP_GX_UPW);
+  for (int b0 = 0; b0 < bk.nwb; b0 += per) {
+    ga.beta0 = b0;
+    ga.nb = std::min(per, bk.nwb - b0);
+    ga.accum = b0 > 0;
+    ga.coef_out = b0 == 0 ? coef_out : nullptr;
+    const size_t lds = blkp_gx_lds(ga.nb, ga.E, sym, waves);
+    HIPCHK(c, blk_lds_attr(gk, lds));
+    int gpc = 0;
+    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&gpc, (const void*)gk, 64 * waves, lds) != hipSuccess || gpc < 1) gpc = 1;
+    const long long wgs = (items + waves - 1) / waves;
+    const unsigned grid = (unsigned)std::max<long long>(1, std::min<long long>(wgs, (long long)c->ncu * gpc));
+    const int mg = mark_begin(c, 3);
+    hipLaunchKernelGGL(gk, dim3(grid), dim3(64 * waves), lds, c->stream, ga);
+    mark_end(c, mg);
+    HIPCHK(c, hipGetLastError());
+  }
+  return QOC_OK;
+}
 // the interpolating chains (k_blkp_ichain) apply: the interpolation (one control), one live wave block, one state
 // column, and the block's coefficients in the LDS beside four waves' rows (QOC_BLKP_ICHAIN=0: the stored form)
 constexpr int BLKP_ISL = 8;  // slices per chunk
@@ -701,7 +825,8 @@ static int blkp_parts(const qoc_ctx* c) { return std::max(1, std::min(env_int("Q
 // formation, then the chains).  The propagators of two groups are held at a time (the formation of group p + 2 waits
 // for the chains of group p): 2.1 GB at the tunable bus' B = 512 instead of every seed's 4.2 GB.  Returns 1 (nothing
 // launched) when even that does not fit in the free HBM: the Chebyshev block chains then run.
-int blkp_eval_concurrent(qoc_ctx* c, double* d_dJdu, const BlkArgs& bk) {
+int blkp_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu, const BlkArgs& bk) {
+  const bool exact = order == QOC_DUKDP_EXACT;
   TChainArgs gf = tchain_args(c);
   TChainArgs gb = tchain_args(c);
   gb.mu_mode = 1;
@@ -713,12 +838,15 @@ int blkp_eval_concurrent(qoc_ctx* c, double* d_dJdu, const BlkArgs& bk) {
   const size_t slab = (size_t)gmax * per_seed * 256;      // double2 per slab
   BlkpPlan pl;
   if ((r = blkp_plan(c, bk, parts, pl))) return r;
+  if (exact && !pl.interp) return 1;  // no curve to differentiate: the caller's dense path, nothing launched here
   c->ichain_last = blkp_ichain_on(c, bk, pl);
   if (c->ichain_last) {  // both chains interpolate their own propagators: nothing stored
     if ((r = blkp_zero_dead(c, bk))) return r;
     if ((r = blkp_launch_ichain(c, gf, gb, bk, pl.ia, true, 0, nullptr))) return r;
     blkp_forward_done(c);
-    if ((r = blkp_launch_grad(c, bk, d_dJdu, nullptr, c->d_coef_mu))) return r;
+    if ((r = exact ? blkp_launch_grad_exact(c, bk, d_dJdu, nullptr, c->d_coef_mu)
+                   : blkp_launch_grad(c, bk, d_dJdu, nullptr, c->d_coef_mu)))
+      return r;
     c->L_is_mu = true;
     c->last_eval_mode = 7;
     return QOC_OK;
@@ -762,7 +890,9 @@ int blkp_eval_concurrent(qoc_ctx* c, double* d_dJdu, const BlkArgs& bk) {
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->sync_ev[2 * parts], 0));
   }
   blkp_forward_done(c);
-  if ((r = blkp_launch_grad(c, bk, d_dJdu, nullptr, c->d_coef_mu))) return r;
+  if ((r = exact ? blkp_launch_grad_exact(c, bk, d_dJdu, nullptr, c->d_coef_mu)
+                 : blkp_launch_grad(c, bk, d_dJdu, nullptr, c->d_coef_mu)))
+    return r;
   c->L_is_mu = true;
   c->last_eval_mode = 7;
   return QOC_OK;
@@ -802,6 +932,7 @@ int blkp_forward(qoc_ctx* c) {
   c->ichain_last = blkp_ichain_on(c, bk, pl);
   c->ichain_fwd = c->ichain_last != 0;
   c->blkp_fwd_nwb = bk.nwb;
+  c->blkp_fwd_interp = pl.interp;
   if (c->ichain_fwd) {  // the forward chain interpolates its propagators; grape_sensitivity's μ recurrence will too
     if ((r = blkp_zero_dead(c, bk))) return r;
     if ((r = blkp_launch_ichain(c, gf, gf, bk, pl.ia, false, 0, nullptr, pen))) return r;
@@ -838,7 +969,9 @@ int blkp_forward(qoc_ctx* c) {
 }
 
 bool blkp_backward_ok(const qoc_ctx* c, int order) {
-  if (!(c->fwd_kind == 2 && order == 3 && (c->cost_kind == QOC_COST_TRACE || c->cost_kind == QOC_COST_ZCAL) &&
+  // the exact gradient: the derivative of the curve the propagate interpolated on (blkp_exact_on)
+  const bool ord_ok = order == 3 || (order == QOC_DUKDP_EXACT && blkp_exact_on(c) && c->blkp_fwd_interp);
+  if (!(c->fwd_kind == 2 && ord_ok && (c->cost_kind == QOC_COST_TRACE || c->cost_kind == QOC_COST_ZCAL) &&
         (c->ichain_fwd || c->d_blkU)))
     return false;
   const int pmode = blkp_pen_mode(c);
@@ -852,7 +985,8 @@ bool blkp_backward_ok(const qoc_ctx* c, int order) {
 // λ_N = coef ⊙ X_target + s_N, λ_k = U_k^H λ_{k+1} + s_k (src/gradient_computations.jl:46-58), and the gradient reads it
 // as it is.  A source counts every block live; where the propagate ran on other wave blocks (the live ones alone, or
 // the interpolating chains of one block) the propagators of this layout are formed first, from the propagate's u.
-int blkp_backward(qoc_ctx* c, double* d_dJdu, const int* stale) {
+int blkp_backward(qoc_ctx* c, int order, double* d_dJdu, const int* stale) {
+  const bool exact = order == QOC_DUKDP_EXACT;
   const int pmode = blkp_pen_mode(c);
   BlkArgs bk = blk_args(c);
   int r = blk_live(c, bk, c->src_on);
@@ -866,7 +1000,8 @@ int blkp_backward(qoc_ctx* c, double* d_dJdu, const int* stale) {
   gb.mu_mode = lam ? 0 : 1;
   if (bk.nwb != c->blkp_fwd_nwb) {  // the propagators of this layout
     BlkpPlan pl;
-    if ((r = blkp_plan(c, bk, 1, pl))) return r;
+    if ((r = blkp_plan(c, bk, 1, pl))) return r;  // (with this layout's N_i when it interpolates)
+    if (exact && !pl.interp) return 1;            // this layout's series did not converge: nothing launched
     const long long units = (long long)c->B * c->Nt * bk.nwb;
     if ((r = blkp_ensure_store(c, (size_t)units * 256 * sizeof(double2), false))) return r;
     if ((r = blkp_launch_exp(c, pl, 0, units, (double2*)c->d_blkU, 0))) return r;
@@ -885,7 +1020,9 @@ int blkp_backward(qoc_ctx* c, double* d_dJdu, const int* stale) {
     if ((r = blkp_launch_chain<false>(c, pl, gb, bk, (const double2*)c->d_blkU, 0, c->B, 0, c->stream, stale, pen)))
       return r;
   }
-  if ((r = blkp_launch_grad(c, bk, d_dJdu, stale, lam ? nullptr : c->d_coef_mu, lam))) return r;
+  if ((r = exact ? blkp_launch_grad_exact(c, bk, d_dJdu, stale, lam ? nullptr : c->d_coef_mu, lam)
+                 : blkp_launch_grad(c, bk, d_dJdu, stale, lam ? nullptr : c->d_coef_mu, lam)))
+    return r;
   if (c->src_on) c->dead_dirty = true;  // λ_k is nonzero on the rows of blocks that carry no state
   c->L_is_mu = !lam;
   c->last_eval_mode = 7;

@@ -133,7 +133,9 @@ function QOC.propagate(A0, A::Vector{<:AbstractMatrix}, u, x0, cache::MI355XCach
 end
 
 # grape_sensitivity (src/gradient_computations.jl:35-77) on the GPU; the closure dJfinal_dx is
-# evaluated here at x[end] and handed over as λ_{Nt+1} (QOC_COST_EXTERNAL).
+# evaluated here at x[end] and handed over as λ_{Nt+1} (QOC_COST_EXTERNAL).  dUkdp_order = 0 (QOC_DUKDP_EXACT) is the
+# exact Fréchet gradient; with this external cost it runs the dense block exponentials (the segmented eval and the
+# interpolating block propagators of blocks of 5..16 rows take it with the built-in costs, qoc_eval_dev).
 function QOC.grape_sensitivity(A0, A::Vector{<:AbstractMatrix}, dJfinal_dx, u, x0, cache::MI355XCache;
                                dUkdp_order=3, dL_dx=nothing)
     # setup_state_penalty's gradient runs on the GPU; nothing clears a penalty left by an earlier call

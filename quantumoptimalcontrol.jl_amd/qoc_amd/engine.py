@@ -34,7 +34,10 @@ def _order(order) -> int:
 
     "exact" is the derivative of the J the engine computes.  On generators with invariant blocks of <= 3 rows (cavity,
     zz) it stays on the segmented eval (info()["backward"] == "segmented"), at about the cost of order 3;
-    QOC_BLKSEG_EXACT=0 sends it to the dense Fréchet kernel instead, which every other system uses."""
+    QOC_BLKSEG_EXACT=0 sends it to the dense Fréchet kernel instead.  On blocks of 5..16 rows with one control (the
+    tunable bus) it stays on the interpolating block propagators (info()["backward"] == "blocks_prop16"): the
+    derivative of the propagators' own curve in u; QOC_BLKP_EXACT=0, two controls or a control range the interpolation
+    cannot resolve send it to the dense Fréchet kernel, which every other system uses."""
     if isinstance(order, str):
         if order != "exact":
             raise ValueError(f"dUkdp_order must be 1..4 or 'exact' (got {order!r})")

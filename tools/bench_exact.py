@@ -1,18 +1,20 @@
-"""The exact (Fréchet) gradient's cost on the segmented eval (diagnostic, plain timing): evals per second of the fused
-eval_device and of the split propagate + grape_sensitivity at
-  order 3                       the default gradient (k_blkseg_eval, ORD 3)
-  exact                         dUkdp_order = "exact" on the segmented kernel (ORD 0)
+"""The exact (Fréchet) gradient's cost on the segmented eval and on the interpolating block propagators (diagnostic,
+plain timing): evals per second of the fused eval_device and of the split propagate + grape_sensitivity at
+  order 3                       the default gradient (k_blkseg_eval, ORD 3; tunable_bus: k_blkp_grad)
+  exact                         dUkdp_order = "exact" on the segmented kernel (ORD 0; tunable_bus: k_blkp_grad_exact)
   exact, QOC_BLKSEG_EXACT=0     the dense Fréchet path (x_k and λ_k rebuilt in HBM, one 2N x 2N block exponential per
-                                slice and control)
+                                slice and control; tunable_bus: QOC_BLKP_EXACT=0)
 on
-  zz      N = 9,  Nt = 500,  B = 512
-  cavity  N = 40, Nt = 1000, B = 256.
+  zz           N = 9,  Nt = 500,  B = 512
+  cavity       N = 40, Nt = 1000, B = 256
+  tunable_bus  N = 27, Nt = 2000, B = 512 (blocks of 13 / 14 rows, one control); its exact legs also print the gradient
+               kernel's own time per eval (phase "k_grad" of phase_times, a profiled pass after the timed ones).
 Warm-up, then K timed steps between two synchronisations, 3 repeats, every repeat printed, one process at a time.
 A library from before the segmented exact gradient ignores the switch: run from a checkout of that commit, the two exact
 legs both time its dense path (the fourth leg of DESIGN.md's table).
 The dense path is orders of magnitude slower; --dense-steps / --dense-warm shorten the legs that leave the segmented
 path (each step there is long enough to time on its own), the segmented legs always run --steps and the full warm-up.
-Usage: python tools/bench_exact.py [zz|cavity ...] [--steps K] [--dense-steps K2] [--dense-warm W2]"""
+Usage: python tools/bench_exact.py [zz|cavity|tunable_bus ...] [--steps K] [--dense-steps K2] [--dense-warm W2]"""
 import os
 import sys
 import time
@@ -38,19 +40,24 @@ K = max(200, opt(args, "--steps", 200))
 K_DENSE = max(1, opt(args, "--dense-steps", K))
 WARM, REPEATS = 20, 3
 WARM_DENSE = max(1, opt(args, "--dense-warm", WARM))
-cfgs = args or ["zz", "cavity"]
+cfgs = args or ["zz", "cavity", "tunable_bus"]
 
 
 def setup(cfg):
-    mk_prob, mk_u, B = systems.CONFIGS["zz_batch" if cfg == "zz" else "cavity"]
+    mk_prob, mk_u, B = systems.CONFIGS["zz_batch" if cfg == "zz" else cfg]
     return mk_prob(), mk_u(B, 0), B
 
 
+def fast_path(cfg):  # (the switch that leaves it, what info()["backward"] reports on it)
+    return ("QOC_BLKP_EXACT", "blocks_prop16") if cfg == "tunable_bus" else ("QOC_BLKSEG_EXACT", "segmented")
+
+
 def leg(cfg, prob, u, B, order, switch):
+    var, fast = fast_path(cfg)
     if switch is None:
-        os.environ.pop("QOC_BLKSEG_EXACT", None)
+        os.environ.pop(var, None)
     else:
-        os.environ["QOC_BLKSEG_EXACT"] = switch
+        os.environ[var] = switch
     eng = GrapeEngine(prob.A0, prob.A, prob.x0, prob.Nt, B=B)
     eng.set_cost_trace(prob.x_target, prob.n)
     ud = torch.from_numpy(np.ascontiguousarray(np.transpose(u, (0, 2, 1)))).cuda()
@@ -65,12 +72,12 @@ def leg(cfg, prob, u, B, order, switch):
         eng.grape_sensitivity_device(ud.data_ptr(), order, gd.data_ptr())
 
     out = {}
-    tag = f"order {order}" if switch is None else f"order {order} QOC_BLKSEG_EXACT={switch}"
+    tag = f"order {order}" if switch is None else f"order {order} {var}={switch}"
     for form, step in (("fused", fused), ("split", split)):
         step()
         eng.synchronize()
         info = eng.info()
-        seg = info["backward"] == "segmented"
+        seg = info["backward"] == fast
         warm, steps = (WARM, K) if seg else (WARM_DENSE, K_DENSE)
         for _ in range(warm - 1):
             step()
@@ -90,6 +97,16 @@ def leg(cfg, prob, u, B, order, switch):
         print(f"{cfg} {form:5s} {tag:32s} backward={info['backward']} split_forward={info['split_forward']} "
               f"steps={steps} J[0]={Jd[0].item():.15g} |g[0]|={gn:.15g} "
               + " ".join(f"{r / 1e6:.6f}" for r in rates) + " M evals/s", flush=True)
+        if cfg == "tunable_bus" and seg:  # the gradient kernel's own time, from events around its launches
+            eng.set_profiling(True)
+            eng.phase_times(reset=True)
+            for _ in range(10):
+                step()
+            eng.synchronize()
+            pt = eng.phase_times(reset=True)
+            eng.set_profiling(False)
+            print(f"{cfg} {form:5s} {tag:32s} per eval of {B} seeds: "
+                  + " ".join(f"{k} {ms / 10:.3f} ms ({n // 10} launches)" for k, (ms, n) in pt.items()), flush=True)
     eng.close()
     return out
 
@@ -102,5 +119,5 @@ for cfg in cfgs:
     dn = leg(cfg, prob, u, B, "exact", "0")
     for form in ("fused", "split"):
         print(f"{cfg} {form}: exact / order 3 (medians) = {np.median(ex[form]) / np.median(o3[form]):.3f}; "
-              f"worst exact repeat / best QOC_BLKSEG_EXACT=0 repeat = {min(ex[form]) / max(dn[form]):.1f}", flush=True)
-os.environ.pop("QOC_BLKSEG_EXACT", None)
+              f"worst exact repeat / best {fast_path(cfg)[0]}=0 repeat = {min(ex[form]) / max(dn[form]):.1f}", flush=True)
+    os.environ.pop(fast_path(cfg)[0], None)

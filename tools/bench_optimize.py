@@ -2,7 +2,8 @@
 
 Settings of the reference driver (examples/zz_coupling_ipopt_exp.jl:56-80) on zz: Nt = 100, 10 splines,
 |c| <= 2 pi 0.06, g_U = [2, 1], 150 L-BFGS iterations per round, B = 512 perturbed starts; and a cavity leg
-(N = 40, Nt = 1000, 20 splines, |c| <= 0.05, B = 256).  In one process, alternating, REPEATS times each after a warm-up:
+(N = 40, Nt = 1000, 20 splines, |c| <= 0.05, B = 256); and a tunable-bus leg (N = 27, Nt = 2000, one flux control on
+20 splines, 0.3 <= c <= 1.0 as tunable_bus_controls draws it, no norm constraints, B = 512).  In one process, alternating, REPEATS times each after a warm-up:
   (a) lockstep  minimize_batched on SplineGrape: batched torch on the host's schedule
   (b) device    minimize_on_device: per-seed state machines, one eval + one fused step kernel per tick
   (c) bare      as many eval_spline_device calls as (b) used ticks, one synchronisation at the end
@@ -10,9 +11,9 @@ Wall time is taken between device synchronisations.  Reported per leg: wall seco
 ticks, seed-evals/s, iterations/s, best f; and (b)/(c), the cost of a tick over a bare eval, and the share of (b)'s
 seed-ticks spent on seeds that were already done.  Writes profiles/bench_optimize_<tag>.json.
 --order 3|exact: the gradient every leg runs on (dUkdp_order; "exact" is the derivative of the computed f, and on these
-two systems stays on the segmented eval); the device leg also reports its failed line searches and their share of its
+two systems stays on the segmented eval, on the tunable bus on the interpolating block propagators); the device leg also reports its failed line searches and their share of its
 seed-ticks (each failed search spends max_ls = 12 trials).
-Usage: python tools/bench_optimize.py [zz|cavity ...] [--tag TAG] [--repeats R] [--B B] [--max-iter K] [--outer R]
+Usage: python tools/bench_optimize.py [zz|cavity|tunable_bus ...] [--tag TAG] [--repeats R] [--B B] [--max-iter K] [--outer R]
        [--order 3|exact]"""
 import json
 import os
@@ -55,6 +56,11 @@ def setup(cfg):
         Bs = systems.spline_matrix(10.0, prob.Nt, ns)
         bound = 2 * np.pi * 0.060
         c0 = np.concatenate([0.01 * np.ones((B, ns)), np.zeros((B, ns))], 1) + 0.02 * rng.standard_normal((B, 2 * ns))
+    elif cfg == "tunable_bus":
+        prob, ns, B = systems.CONFIGS["tunable_bus"][0](), 20, B_OVERRIDE or 512
+        Bs = systems.spline_matrix(350.0, prob.Nt, ns)
+        c0 = rng.uniform(0.4, 0.9, size=(B, ns))
+        return prob, Bs, c0, B, dict(lower=0.3, upper=1.0, max_iter=MAX_ITER, outer_iters=1)
     else:
         prob, ns, B = systems.CONFIGS["cavity"][0](), 20, B_OVERRIDE or 256
         Bs = systems.spline_matrix(float(prob.Nt), prob.Nt, ns)
@@ -80,7 +86,7 @@ def run(cfg):
     state = {"ticks": 0}
 
     def lockstep():
-        r = minimize_batched(sg.fg, c0d, cons=sg.cons, **kw)
+        r = minimize_batched(sg.fg, c0d, cons=sg.cons if "g_upper" in kw else None, **kw)
         return dict(batched_evals=r.n_evals, seed_evals=B * r.n_evals, iterations=B * len(r.history),
                     best_f=float(r.f.min()), converged=int(r.converged.sum()))
 
@@ -125,7 +131,7 @@ def run(cfg):
     out["device_over_bare"] = [x / y for x, y in zip(b, c)]
     out["lockstep_best_over_device_worst"] = min(a) / max(b)
     out["every_device_repeat_beats_best_lockstep"] = bool(max(b) < min(a))
-    out["settings"] = dict(cfg=cfg, B=B, N=prob.N, Nt=prob.Nt, ns=Bs.shape[1], max_iter=MAX_ITER, outer_iters=OUTER,
+    out["settings"] = dict(cfg=cfg, B=B, N=prob.N, Nt=prob.Nt, ns=Bs.shape[1], max_iter=MAX_ITER, outer_iters=kw["outer_iters"],
                            order=ORDER, backward=info["backward"])
     print(f"{cfg}: tick / bare eval = " + " ".join(f"{r:.3f}" for r in out["device_over_bare"])
           + f"; best lockstep / worst device = {out['lockstep_best_over_device_worst']:.1f}; seed-ticks on done seeds "
