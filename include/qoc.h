@@ -138,7 +138,13 @@ int qoc_sensitivity_spline(qoc_ctx* ctx, const double* c, int dUkdp_order, doubl
  * device pointers: d_g (B x 2), d_gjac (B x 2 x nc, constraint-major = Ipopt's dense triplet order; may be NULL). */
 int qoc_spline_constraints_dev(qoc_ctx* ctx, const double* d_c, double* d_g, double* d_gjac);
 
-/* Lazy readback of cache fields (test/test_gradient_computation.jl:84,86 read cache.x / cache.λ). */
+/* Lazy readback of cache fields (test/test_gradient_computation.jl:84,86 read cache.x / cache.λ).
+ * qoc_get_states: x_k of the last propagate / eval; QOC_ERR_STATE once qoc_set_generators, qoc_set_x0, qoc_set_cost or
+ * qoc_set_compression has invalidated it (qoc_set_state_penalty and qoc_set_costate_source keep it).
+ * qoc_get_costates: λ_k of the last grape_sensitivity / eval, under the settings of that call: any setter and any later
+ * propagate leave them as they are (zeros before the first one).
+ * An entry point that returns an error has changed nothing the later calls see: a stale or refused
+ * grape_sensitivity leaves the co-states, a refused eval the controls and states of the last propagate. */
 int qoc_get_states(qoc_ctx* ctx, int seed, int k, double* x_out);       /* k in [0,Nt], -1 = final */
 int qoc_get_costates(qoc_ctx* ctx, int seed, int k, double* lam_out);
 int qoc_get_propagator(qoc_ctx* ctx, int seed, int k, double* U_out);   /* Uk_vec[k+1], k in [0,Nt) */

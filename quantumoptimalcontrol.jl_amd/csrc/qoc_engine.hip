@@ -1230,13 +1230,19 @@ int qoc_eval_spline_dev(qoc_ctx* c, const double* d_c, int order, double* d_J, d
   if (!c) return fail(nullptr, QOC_ERR_ARG, "null context");
   if (!c->ns) return fail(c, QOC_ERR_STATE, "spline basis not set (qoc_set_spline_basis)");
   if (!d_c) return fail(c, QOC_ERR_ARG, "d_c is null");
-  HIPCHK(c, hipSetDevice(c->dev));
+  // everything qoc_eval_dev refuses is refused here, before the spline map overwrites d_u: the states of the last
+  // propagate, and a grape_sensitivity on them, still belong to the u that is there
+  int r = check_ready(c);
+  if (r) return r;
+  if (c->cost_kind == QOC_COST_EXTERNAL)
+    return fail(c, QOC_ERR_STATE, "qoc_eval_spline_dev needs a device-side cost (TRACE or ZCAL)");
+  if (order < 0 || order > 4) return fail(c, QOC_ERR_ARG, "dUkdp_order must be 1..4 or QOC_DUKDP_EXACT (got %d)", order);
   const long long nuT = (long long)c->B * c->Nt * c->nu;
   const unsigned blocks = (unsigned)std::min<long long>((nuT + 255) / 256, 4096);
   hipLaunchKernelGGL(k_spline_u, dim3(blocks), dim3(256), 0, c->stream, c->B, c->Nt, c->ns, c->nu, c->d_Bs, d_c,
                      c->d_u);
   HIPCHK(c, hipGetLastError());
-  int r = qoc_eval_dev(c, c->d_u, order, d_J, c->d_dJdu);
+  r = qoc_eval_dev(c, c->d_u, order, d_J, c->d_dJdu);
   if (r) return r;
   if (d_dJdc) {
     const long long outs = (long long)c->B * c->ns * c->nu;

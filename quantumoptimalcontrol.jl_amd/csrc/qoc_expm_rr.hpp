@@ -464,6 +464,10 @@ __device__ __forceinline__ void expm_rr_unit(int unit, int N, int nu, const cx<T
     };
     Own Bx;
     make_Bps(tr, V);
+    // rmul's left operand must be zero outside N: its k-steps run to 4 ceil(N / 4), and at an even N make_Bps read
+    // column N from the pitch's pad, which nothing writes (a NaN left there by another kernel times the zero rows
+    // of A3 is a NaN in every column of that row).  The B_i below are addends only; rmul masks its result.
+    mask_own(V);
     for (int i = tr - 1; i >= 0; --i) {
       make_Bps(i, Bx);
       E::template rmul<KS>(N, V, Xr, Xi, V, Bx, lane);  // = A3 V + B_i (polynomials in A commute)

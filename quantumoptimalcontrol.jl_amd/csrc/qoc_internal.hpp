@@ -253,9 +253,9 @@ struct qoc_ctx {
   std::vector<int> h_wrow_live, h_dead_rows;
   double* d_gc_part = nullptr;   // large-N gradient: per (slice, column block) partial traces (k_gen_contract2)
   size_t gc_part_bytes = 0;
-  // the dead rows known to hold zeros in the six state-shaped buffers (blk_zero_dead), and those buffers: a backward
-  // with an external λ_N or a co-state source (the only writers of nonzero values into rows whose x0 and target are
-  // zero) sets dead_dirty
+  // the dead rows known to hold zeros (blk_zero_dead) and the state-shaped buffers, up to six, that hold them there:
+  // a backward with an external λ_N or a co-state source (the only writers of nonzero values into rows whose x0 and
+  // target are zero) sets dead_dirty, after which no buffer counts
   std::vector<int> h_dead_zeroed;
   const void* dead_bufs[6] = {};
   bool dead_dirty = true;
@@ -418,6 +418,8 @@ int blk_materialize(qoc_ctx* c);  // rebuild every lazily kept x_k / λ_k (befor
 bool blk_live_rows(const qoc_ctx* c, std::vector<int>& wl, std::vector<int>& dead);
 int blk_live(qoc_ctx* c, BlkArgs& bk, bool all = false);
 int blk_zero_dead(qoc_ctx* c, std::initializer_list<void*> bufs);
+bool blk_dead_pending(const qoc_ctx* c, const void* buf);  // blk_zero_dead would write buf
+int wait_stale_check(qoc_ctx* c);                          // qoc_engine.hip: the host's wait for a queued stale-u check
 
 // ---- qoc_run_blkp.hip ----
 int blkp_pen_mode(const qoc_ctx* c);  // a penalty / co-state source: 0 none in effect, 1 the PEN chains, 2 Chebyshev

@@ -262,26 +262,36 @@ int blk_live(qoc_ctx* c, BlkArgs& bk, bool all) {
   bk.nwb = (int)(wl.size() / 16);
   return QOC_OK;
 }
-// the dead rows' zeros (blk_live) in up to six state-shaped buffers of B (Nt + 1) m columns.  Skipped when the same
-// buffers already hold zeros on the same rows: every exact recurrence keeps rows whose x0 and target are zero at zero
+// the dead rows' zeros (blk_live) in up to six state-shaped buffers of B (Nt + 1) m columns.  A buffer that already
+// holds zeros on the same rows is skipped: every exact recurrence keeps rows whose x0 and target are zero at zero
 // (the generators keep the blocks invariant), so only a backward with an external λ_N or a co-state source
-// (dead_dirty), new generators or a reallocated buffer can put anything else there.
+// (dead_dirty), new generators or a reallocated buffer can put anything else there.  Each caller names the buffers it
+// is about to write and no others: a propagate leaves d_L, the co-states of the last grape_sensitivity (which
+// qoc_get_costates still answers for, and which may live on rows that are dead by now), as it is.
+bool blk_dead_pending(const qoc_ctx* c, const void* buf) {
+  if (c->dead_dirty || c->h_dead_zeroed != c->h_dead_rows) return true;
+  return std::find(std::begin(c->dead_bufs), std::end(c->dead_bufs), buf) == std::end(c->dead_bufs);
+}
 int blk_zero_dead(qoc_ctx* c, std::initializer_list<void*> bufs) {
   ZeroRows z{};
   for (void* p : bufs)
-    if (p && z.nbuf < 6) z.buf[z.nbuf++] = (double2*)p;
-  bool same = !c->dead_dirty && c->h_dead_zeroed == c->h_dead_rows;
-  for (int i = 0; i < 6; ++i) same = same && c->dead_bufs[i] == (i < z.nbuf ? (const void*)z.buf[i] : nullptr);
-  if (same) return QOC_OK;
+    if (p && z.nbuf < 6 && blk_dead_pending(c, p)) z.buf[z.nbuf++] = (double2*)p;
+  if (c->dead_dirty || c->h_dead_zeroed != c->h_dead_rows)  // what the other buffers hold there is unknown now
+    for (const void*& p : c->dead_bufs) p = nullptr;
+  c->h_dead_zeroed = c->h_dead_rows;
+  c->dead_dirty = false;
+  if (!z.nbuf) return QOC_OK;
   const long long cols = (long long)c->B * (c->Nt + 1) * c->m;
   const long long total = cols * (long long)c->h_dead_rows.size();
   const unsigned grid = (unsigned)std::min<long long>((total + 255) / 256, 4096);
   hipLaunchKernelGGL(k_zero_rows, dim3(grid), dim3(256), 0, c->stream, z, cols, c->N, c->d_dead_rows,
                      (int)c->h_dead_rows.size());
   HIPCHK(c, hipGetLastError());
-  c->h_dead_zeroed = c->h_dead_rows;
-  for (int i = 0; i < 6; ++i) c->dead_bufs[i] = i < z.nbuf ? (const void*)z.buf[i] : nullptr;
-  c->dead_dirty = false;
+  for (int i = 0; i < z.nbuf; ++i) {  // into a free slot (six buffers at the most are ever named: d_X, d_L, four captures)
+    const void** slot = std::find(std::begin(c->dead_bufs), std::end(c->dead_bufs), (const void*)nullptr);
+    if (slot == std::end(c->dead_bufs)) slot = c->dead_bufs + i;
+    *slot = z.buf[i];
+  }
   return QOC_OK;
 }
 

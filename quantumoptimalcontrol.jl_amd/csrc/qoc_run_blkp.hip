@@ -43,8 +43,10 @@ int blkp_pen_mode(const qoc_ctx* c) {
 }
 
 // the dead rows' zeros in x_k and λ_k when the launch runs on the live blocks alone
-static int blkp_zero_dead(qoc_ctx* c, const BlkArgs& bk) {
-  return bk.nwb != c->nwb ? blk_zero_dead(c, {c->d_X, c->d_L}) : QOC_OK;
+// lam: the caller writes the co-states too (an eval, a grape_sensitivity); a propagate leaves d_L alone
+static int blkp_zero_dead(qoc_ctx* c, const BlkArgs& bk, bool lam) {
+  if (bk.nwb == c->nwb) return QOC_OK;
+  return lam ? blk_zero_dead(c, {c->d_X, c->d_L}) : blk_zero_dead(c, {c->d_X});
 }
 // a forward from propagators formed without step records: d_steps still holds the last k_tchain_prep's records, not
 // this u's (the Chebyshev backward re-preps first)
@@ -841,7 +843,7 @@ int blkp_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu, const BlkArgs& b
   if (exact && !pl.interp) return 1;  // no curve to differentiate: the caller's dense path, nothing launched here
   c->ichain_last = blkp_ichain_on(c, bk, pl);
   if (c->ichain_last) {  // both chains interpolate their own propagators: nothing stored
-    if ((r = blkp_zero_dead(c, bk))) return r;
+    if ((r = blkp_zero_dead(c, bk, true))) return r;
     if ((r = blkp_launch_ichain(c, gf, gb, bk, pl.ia, true, 0, nullptr))) return r;
     blkp_forward_done(c);
     if ((r = exact ? blkp_launch_grad_exact(c, bk, d_dJdu, nullptr, c->d_coef_mu)
@@ -852,7 +854,7 @@ int blkp_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu, const BlkArgs& b
     return QOC_OK;
   }
   if ((r = blkp_ensure_store(c, nslab * slab * sizeof(double2), true))) return r;  // 1: does not fit
-  if ((r = blkp_zero_dead(c, bk))) return r;
+  if ((r = blkp_zero_dead(c, bk, true))) return r;
   // events: [p] group p formed, [parts + p] group p's chains done, [2 parts] everything queued before
   if (parts > 1) {
     if ((r = ensure_stream2(c, 2 * parts + 1))) return r;
@@ -934,14 +936,14 @@ int blkp_forward(qoc_ctx* c) {
   c->blkp_fwd_nwb = bk.nwb;
   c->blkp_fwd_interp = pl.interp;
   if (c->ichain_fwd) {  // the forward chain interpolates its propagators; grape_sensitivity's μ recurrence will too
-    if ((r = blkp_zero_dead(c, bk))) return r;
+    if ((r = blkp_zero_dead(c, bk, false))) return r;
     if ((r = blkp_launch_ichain(c, gf, gf, bk, pl.ia, false, 0, nullptr, pen))) return r;
     blkp_forward_done(c);
     c->fwd_kind = 2;
     return QOC_OK;
   }
   if ((r = blkp_ensure_store(c, (size_t)c->B * per_seed * 256 * sizeof(double2), true))) return r;
-  if ((r = blkp_zero_dead(c, bk))) return r;
+  if ((r = blkp_zero_dead(c, bk, false))) return r;
   if (parts > 1) {
     if ((r = ensure_stream2(c, parts + 1))) return r;
     HIPCHK(c, hipEventRecord(c->sync_ev[parts], c->stream));
@@ -1009,7 +1011,12 @@ int blkp_backward(qoc_ctx* c, int order, double* d_dJdu, const int* stale) {
     c->ichain_last = 0;
     c->blkp_fwd_nwb = bk.nwb;
   }
-  if ((r = blkp_zero_dead(c, bk))) return r;  // (a no-op unless a sourced backward left λ on the dead rows)
+  // the dead rows of d_L (a no-op unless a sourced backward, or co-states from before x0 or the target moved to another
+  // block, left λ there).  k_zero_rows reads no stale flag, and a refused call must leave the last grape_sensitivity's
+  // co-states as they are: when there is something to zero, the host waits for the check first
+  if (stale && bk.nwb != c->nwb && blk_dead_pending(c, c->d_L))
+    if (const int w = wait_stale_check(c)) return w;
+  if ((r = blkp_zero_dead(c, bk, true))) return r;
   if (c->ichain_fwd) {  // the propagate interpolated: the μ recurrence from the same coefficients (the same u)
     BlkpIntArgs ia;
     blkp_interp_args(c, bk, ia);
