@@ -43,7 +43,17 @@ extern "C" {
  * interpolating block propagators' own curve, dU/du = e^{mu(u)} sum_i T_i(xi) N_i, on the stored / interpolating
  * propagators (fused and split call forms, penalty and co-state source, TRACE and ZCAL; QOC_BLKP_EXACT=0 off).
  * Elsewhere (two controls on such blocks, a control range the interpolation cannot resolve, QOC_BLKP_INTERP=0,
- * QOC_BLKP=0, QOC_COST_EXTERNAL), or with QOC_BLKSEG_EXACT=0, one 2N x 2N block exponential per slice and control. */
+ * QOC_BLKP=0, QOC_COST_EXTERNAL), or with QOC_BLKSEG_EXACT=0, one 2N x 2N block exponential per slice and control.
+ * On dense generators (no block path: none detected, or QOC_BLOCKS=0) that the fused gradient kernels fit (fp64,
+ * N <= 48, m in {1, 2, 4, 8, 16}, nu <= 2, QOC_PROP_EXPM) it is the series
+ *   Re Σ_{a+b < n_k} <(Ã_k^H)^a λ', A_j Ã_k^b x_k> / (a+b+1)!   (Ã_k = A_k - μ_k I, λ' = conj(e^{μ_k}) λ_{k+1})
+ * run on MFMA with no exponential formed, n_k per slice from the chain prep's bound ρ_k (tail below 2^-53).  Its
+ * rounding error grows like e^ρ ε, so a call whose largest n_k exceeds 48 (ρ ≈ 8.6) runs the block exponential
+ * instead, whole.  That decision needs the largest n_k on the host: every exact gradient on such a context copies 16
+ * bytes back and synchronises the stream once, also in qoc_eval_dev (orders 1-4 and the block paths queue as before).
+ * QOC_GRAD_EXACT_SERIES=0 at qoc_create keeps the block exponential; QOC_GRAD_EXACT_WS_MB bounds the series'
+ * workspace (default min(2 GiB, free / 8)), which only changes how many slices one launch pair covers.
+ * qoc_exact_series_stats reports what ran. */
 #define QOC_DUKDP_EXACT 0
 
 #define QOC_COST_TRACE 0     /* J = 1-|tr(X'x)|^2/n^2            (src/penalty_fcns.jl:15-24) */
@@ -247,6 +257,12 @@ int qoc_get_info_n(qoc_ctx* ctx, long long* info, int n);
 int qoc_set_chain(qoc_ctx* ctx, int mode);
 /* Taylor terms executed per direction (Σ over slices of P s) since the last reset (QOC_CHAIN_TAYLOR). */
 int qoc_chain_terms(qoc_ctx* ctx, long long* terms, int reset);
+/* The exact gradient's series route on dense generators (QOC_DUKDP_EXACT above) since the last reset:
+ * stats[0] = (seed, slice) units the series kernels processed, stats[1] = Σ n_k over them (terms per side),
+ * stats[2] = the largest n_k among them, stats[3] = calls that fell back to the block exponential because their
+ * largest n_k exceeded the cap of 48.  Host counters: no device work, no synchronisation.  QOC_ERR_ARG for a NULL
+ * context or buffer. */
+int qoc_exact_series_stats(qoc_ctx* ctx, long long* stats /*[4]*/, int reset);
 
 /* Multi-GPU epilogue: seeds are sharded contiguously over ranks, one context per GPU; the
  * only exchange is an all-gather of each rank's best (J, global seed id) over RCCL (xGMI), 16 bytes per rank.

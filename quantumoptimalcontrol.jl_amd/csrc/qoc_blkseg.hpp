@@ -210,25 +210,8 @@ struct BlksegTrig {
 // within [-ρ, ρ]).  K = 5 up to ρ = 0.24, 7 up to 0.66, else 9 (covers θ_cap ≈ 0.98); the bounds leave margin
 // (exact limits 0.248 / 0.684 / 1.32).
 __host__ __device__ constexpr int blkseg_series_k(double rho) { return rho <= 0.24 ? 5 : rho <= 0.66 ? 7 : BLKSEG_KMAX; }
-// The exact gradient's generic series (seg_contract_exact): the number of orders n = a + b of
-// M = Σ_{a,b} X^b K X^a / (a+b+1)! to run for a seed whose shifted generators have spectral half-width <= ρ.  Order n
-// has n + 1 words of norm <= ρ^n |K| each, so it is bounded by ρ^n / n! |K| (which covers the rule Σ_{n >= n_ex}
-// ρ^n / (n+1)! <= 2^-53 with room), and the tail behind n_ex by ρ^n_ex / n_ex! / (1 - ρ / (n_ex + 1)).  The smallest
-// n_ex whose bound is <= 2^-53: 9 at ρ = 0.063 (zz, Nt = 500), 11 at 0.17 (cavity, Nt = 1000), 20 at 1.25.  X is
-// skew-Hermitian, so the partial sums grow to e^ρ at most before they fall: the rounding error is e^ρ ε, and the
-// cap of 64 orders (ρ ≈ 16) is far beyond what the fp64 bar allows anyway.
-constexpr int BLKSEG_NEX_MAX = 64;
-__host__ __device__ inline int blkseg_exact_terms(double rho) {
-  const double tol = 1.1102230246251565e-16;
-  double term = 1.0;  // ρ^n / n!
-  int n = 0;
-  while (n < BLKSEG_NEX_MAX) {
-    if (n >= 1 && rho < n + 1 && term <= tol * (1.0 - rho / (n + 1))) break;
-    ++n;
-    term *= rho / n;
-  }
-  return n;
-}
+// blkseg_exact_terms, the exact gradient's term-count rule (seg_contract_exact), lives in qoc_common.hpp: the dense
+// series kernels (qoc_grad_rr.hpp) share it.
 constexpr BlksegTrig blkseg_trig() {
   BlksegTrig t{};
   double f = 1.0;  // 1 / n!

@@ -35,6 +35,26 @@ __device__ __forceinline__ cx<T> cinv(cx<T> d) {
   return {d.r * s, -d.i * s};
 }
 
+// The exact gradient's generic series (seg_contract_exact): the number of orders n = a + b of
+// M = Σ_{a,b} X^b K X^a / (a+b+1)! to run for a seed whose shifted generators have spectral half-width <= ρ.  Order n
+// has n + 1 words of norm <= ρ^n |K| each, so it is bounded by ρ^n / n! |K| (which covers the rule Σ_{n >= n_ex}
+// ρ^n / (n+1)! <= 2^-53 with room), and the tail behind n_ex by ρ^n_ex / n_ex! / (1 - ρ / (n_ex + 1)).  The smallest
+// n_ex whose bound is <= 2^-53: 9 at ρ = 0.063 (zz, Nt = 500), 11 at 0.17 (cavity, Nt = 1000), 20 at 1.25.  X is
+// skew-Hermitian, so the partial sums grow to e^ρ at most before they fall: the rounding error is e^ρ ε, and the
+// cap of 64 orders (ρ ≈ 16) is far beyond what the fp64 bar allows anyway.
+constexpr int BLKSEG_NEX_MAX = 64;
+__host__ __device__ inline int blkseg_exact_terms(double rho) {
+  const double tol = 1.1102230246251565e-16;
+  double term = 1.0;  // ρ^n / n!
+  int n = 0;
+  while (n < BLKSEG_NEX_MAX) {
+    if (n >= 1 && rho < n + 1 && term <= tol * (1.0 - rho / (n + 1))) break;
+    ++n;
+    term *= rho / n;
+  }
+  return n;
+}
+
 // ---------------------------------------------------------------------------
 // MFMA wrappers.  A operand: lane l holds A[l&15][k=l>>4]; B operand: B[k=l>>4][l&15].
 // D layout differs by dtype (cdna_hip_programming.md §3):

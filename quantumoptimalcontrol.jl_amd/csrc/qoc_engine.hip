@@ -545,6 +545,7 @@ int qoc_create(qoc_ctx** out, int device, int N, int m, int nu, int Nt, int B, i
   c->bwd_prestate = env_int("QOC_BWD_PRESTATE", c->bwd_prestate);
   if (env_set("QOC_CONCURRENT")) c->concurrent = std::max(0, std::min(2, env_int("QOC_CONCURRENT", 0)));
   c->tchain_rot = env_int("QOC_TCHAIN_ROT", c->tchain_rot);
+  c->exact_series = env_int("QOC_GRAD_EXACT_SERIES", 1) != 0;
   hipMemset(c->d_L, 0, (size_t)B * (Nt + 1) * Nm * c->esz);
   *out = c;
   return QOC_OK;
@@ -574,7 +575,7 @@ void qoc_destroy(qoc_ctx* c) {
   if (c->h_flag) hipHostFree(c->h_flag);
   if (c->flag_ev) hipEventDestroy(c->flag_ev);
   void* ptrs[] = {c->d_A, c->d_x0, c->d_Xt, c->d_pmask, c->d_u,    c->d_U,    c->d_X, c->d_L, c->d_u_lam, c->d_coef_lam, c->d_blkU, c->d_J_scr, c->d_coef_scr,
-                  c->d_J, c->d_coef, c->d_dJdu, c->d_flag, c->d_hist, c->d_stage, c->d_ws, c->d_red, c->d_Bs, c->d_cstage, c->d_fws, c->d_AH, c->d_Cst, c->d_gws, c->d_pws, c->d_ps, c->d_At, c->d_steps, c->d_terms, c->d_src, c->d_rsec, c->d_sink, c->d_blkrec};
+                  c->d_J, c->d_coef, c->d_dJdu, c->d_flag, c->d_hist, c->d_stage, c->d_ws, c->d_red, c->d_Bs, c->d_cstage, c->d_fws, c->d_AH, c->d_Cst, c->d_gws, c->d_pws, c->d_ps, c->d_At, c->d_steps, c->d_terms, c->d_src, c->d_rsec, c->d_sink, c->d_blkrec, c->d_xn};
   for (void* p : ptrs)
     if (p) hipFree(p);
   for (auto& m : c->marks) {
@@ -664,7 +665,9 @@ int qoc_set_generators(qoc_ctx* c, const double* A0, const double* const* Aj) {
       c->big_rho_ok = true;
     }
   }
-  if (c->tchain_ok) {  // shifted generators Ã_j = A_j - μ_j I and their norms for the Taylor-action chains
+  // shifted generators Ã_j = A_j - μ_j I and their norms for the Taylor-action chains; the exact series gradient
+  // (grad_rr_exact) takes the shifts and bounds on every shape the fused gradient fits, also without those chains
+  if (c->tchain_ok || c->grad_rr_any_m) {
     tchain_thresholds(c->tprm, c->prec);
     c->cap_ok = c->prec == QOC_FP64 && env_int("QOC_CAPTURE", 1) != 0;
     c->tprm.pmin = c->cap_ok ? 2 : 1;  // the captured products are the first two of every slice
@@ -721,6 +724,7 @@ int qoc_set_generators(qoc_ctx* c, const double* A0, const double* const* Aj) {
       }
       c->tprm.mur[j] = mr;
       c->tprm.mui[j] = mi;
+      if (!c->tchain_ok) continue;
       r = upload(c, sh.data(), (char*)c->d_At + j * NN * c->esz, NN);
       if (r == QOC_OK) HIPCHK(c, hipStreamSynchronize(c->stream));  // sh is reused
     }
@@ -731,7 +735,10 @@ int qoc_set_generators(qoc_ctx* c, const double* A0, const double* const* Aj) {
     // up to ρ_0 = 25 without substeps (cavity 0.15, zz 0.05, tunable bus 9.1: measured faster than Padé-13
     // propagators there too), the Taylor variant while ||Ã_0||_1 <= 1; larger norms form propagators on MFMA
     const bool cheb_run = c->cheb && tchain_mf(c);
-    if (c->chain_req != QOC_CHAIN_AUTO) c->chain_mode = c->chain_req;
+    if (!c->tchain_ok) {  // only tprm's shifts and bounds are in use: every chain switch as without them
+      c->chain_mode = 0;
+      c->cap_ok = c->cheb_ok = c->cheb = c->skew_exact = false;
+    } else if (c->chain_req != QOC_CHAIN_AUTO) c->chain_mode = c->chain_req;
     else if (env_is("QOC_CHAIN", "taylor")) c->chain_mode = 1;
     else if (env_is("QOC_CHAIN", "expm")) c->chain_mode = 0;
     else c->chain_mode = (cheb_run ? c->tprm.rad[0] <= 25.0 : c->tprm.nrm[0] <= 1.0) ? 1 : 0;
@@ -1538,6 +1545,14 @@ int qoc_chain_terms(qoc_ctx* c, long long* terms, int reset) {
   unsigned long long t = 0;
   for (int i = 0; i < TERM_SLOTS; ++i) t += part[i];
   *terms = (long long)t;
+  return QOC_OK;
+}
+
+int qoc_exact_series_stats(qoc_ctx* c, long long* stats, int reset) {
+  if (!c || !stats) return fail(c, QOC_ERR_ARG, "null argument");
+  for (int i = 0; i < 4; ++i) stats[i] = c->xs_stats[i];  // host counters: grad_rr_exact adds to them after its readback
+  if (reset)
+    for (int i = 0; i < 4; ++i) c->xs_stats[i] = 0;
   return QOC_OK;
 }
 

@@ -1,4 +1,5 @@
-// qoc_grad_rr.hpp — fused order-3 GRAPE gradient, register-resident (N <= 48, 16 % m == 0, nu <= 2).
+// qoc_grad_rr.hpp — fused order-3 GRAPE gradient, register-resident (N <= 48, 16 % m == 0, nu <= 2), and the exact
+// gradient as a series on the same tiles (k_grad_rr_x*, at the end).
 //
 // Replaces expm_jacobian!(dUkdp_order = 3) + _compute_u_sensitivity at
 // src/gradient_computations.jl:61-74,177-223 for every (seed, slice) unit:
@@ -525,6 +526,215 @@ __global__ __launch_bounds__(256, 2) void k_grad_rr_c(const GradCapArgs a) {
 #pragma unroll
     for (int j = 0; j < NU; ++j) {
       double v = sj[j] + s2[j] * (1.0 / 6.0);
+      v += __shfl_xor(v, 16);
+      v += __shfl_xor(v, 32);
+      for (int o = 1; o < m; o <<= 1) v += __shfl_xor(v, o);
+      if (g.ok && lane < 16 && c % m == 0) a.dJdu[g.unit * NU + j] = v;
+    }
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------
+// Exact gradient as a series (k_grad_rr_xn / _xq / _xp): the derivative of exp(A_k) in direction A_j contracted
+// between λ_{k+1} and x_k, with no exponential formed.  With the chains' scalar shift A_k = Ã_k + μ_k I
+// (μ_k = μ_0 + Σ_j u_jk μ_j), λ' = conj(e^{μ_k}) λ_{k+1} and c_n = 1 / (n+1)!:
+//   dJdu[k, j] = Re Σ_{a,b >= 0} c_{a+b} <(Ã_k^H)^a λ', A_j Ã_k^b x_k>,
+// truncated at a + b <= n_k - 1, n_k = blkseg_exact_terms(ρ_k) (qoc_common.hpp; ρ_k the chain prep's bound of Ã_k).
+// The co-state side collapses into one downward recurrence,
+//   R(n) = 0,  R(b) = c_b λ' + Ã_k^H R(b+1),  b = n-1 .. 0          (k_grad_rr_xq, every R(b) to the workspace)
+//   dJdu[k, j] = Re Σ_{b < n} <R(b), A_j q_b>,  q_0 = x_k,  q_{b+1} = Ã_k q_b   (k_grad_rr_xp)
+// i.e. one generator product per term and side plus the nu contractions.  Tile geometry, generators in LDS and the
+// products are those of k_grad_rr_q / _p.  The loop count is wave-uniform, the tile's largest n_k; a lane whose own
+// n_k <= b takes c_b = 0, so its R(b) is exactly zero: a unit's result depends on its own n_k alone, not on its tile
+// mates nor on how the slices were cut into ranges.  The series runs on the unscaled Ã_k, so its rounding error grows
+// like e^ρ ε: the host routes a call whose largest n_k exceeds GRADX_NMAX (ρ ≈ 8.6) to the block exponential.
+constexpr int GRADX_NMAX = 48;
+
+struct GradXCount {
+  int nu;
+  long long units;
+  const double* u;               // B x Nt x nu
+  double rho[3];                 // ρ_k = rho[0] + Σ_j |u_jk| rho[j]
+  int* nterm;                    // n_k per unit
+  unsigned long long* stat;      // [0] max n_k, [1] Σ n_k (zeroed before the launch)
+};
+
+// The term counts: one thread per unit; max and sum reduced per wave, then one atomic pair per wave.
+static __global__ void k_grad_rr_xn(const GradXCount a) {
+  unsigned long long nmax = 0, nsum = 0;
+  for (long long e = blockIdx.x * (long long)blockDim.x + threadIdx.x; e < a.units; e += (long long)gridDim.x * blockDim.x) {
+    double rho = a.rho[0];
+    for (int j = 0; j < a.nu; ++j) rho += fabs(a.u[e * a.nu + j]) * a.rho[j + 1];
+    const int n = blkseg_exact_terms(rho);
+    a.nterm[e] = n;
+    nmax = n > nmax ? (unsigned long long)n : nmax;
+    nsum += (unsigned long long)n;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned long long om = __shfl_xor(nmax, o);
+    nmax = om > nmax ? om : nmax;
+    nsum += __shfl_xor(nsum, o);
+  }
+  if ((threadIdx.x & 63) == 0 && nsum) {
+    atomicMax(a.stat, nmax);
+    atomicAdd(a.stat + 1, nsum);
+  }
+}
+
+struct GradXArgs {
+  int N, m, Nt, B, k0, nk;
+  int nmax;                      // the call's largest n_k: slots of the workspace
+  const void* Agen;              // generators A_j (unshifted), column-major
+  const double* u;               // B x Nt x nu
+  const void* X;                 // states (B x (Nt+1) x N x m)
+  const void* L;                 // co-states
+  void* R;                       // workspace [b][unit in range][column][row]
+  const int* nterm;              // n_k per unit (B x Nt)
+  double mur[3], mui[3];         // shifts μ_j
+  double c[GRADX_NMAX];          // c_b = 1 / (b+1)!
+  double* dJdu;
+};
+
+// what the two series kernels share per tile: the unit's workspace column, its n_k, μ_k and the tile's loop count
+struct GradXTile {
+  size_t wb;   // workspace offset of this lane's column within one R(b)
+  int n;       // this lane's n_k (0 past the last unit)
+  int nt;      // the tile's largest n_k (wave-uniform)
+  double mr, mi;
+};
+template <int NU>
+__device__ __forceinline__ GradXTile gradx_tile(const GradXArgs& a, long long tile, int lane, const GradTile& g,
+                                                const double* uj) {
+  GradXTile x;
+  const int c = lane & 15, upt = 16 / a.m;
+  const long long ul = g.ok ? tile * upt + c / a.m : 0;
+  x.wb = ((size_t)ul * a.m + c % a.m) * a.N;
+  x.n = g.ok ? min(a.nterm[g.unit], a.nmax) : 0;
+  int nt = x.n;
+  for (int o = 32; o > 0; o >>= 1) nt = max(nt, __shfl_xor(nt, o));
+  x.nt = __builtin_amdgcn_readfirstlane(nt);
+  x.mr = a.mur[0];
+  x.mi = a.mui[0];
+#pragma unroll
+  for (int j = 0; j < NU; ++j) {
+    x.mr += uj[j] * a.mur[j + 1];
+    x.mi += uj[j] * a.mui[j + 1];
+  }
+  return x;
+}
+
+// Co-state side: λ' = conj(e^{μ_k}) λ_{k+1}, then R(b) downward; Ã_k^H v = A_k^H v - conj(μ_k) v.
+template <typename T, int NT, int KS, int NU>
+__global__ __launch_bounds__(256, 2) void k_grad_rr_xq(const GradXArgs a) {
+  using G = GradRR<T, NT>;
+  using Own = typename G::Own;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int N = a.N, m = a.m;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int nw = blockDim.x >> 6;
+  T* Gr = reinterpret_cast<T*>(smem);
+  T* Gi = Gr + (size_t)(NU + 1) * N * G::ldp(N);
+  grad_gens_to_lds<T, NT>(N, NU, (const cx<T>*)a.Agen, Gr, Gi);
+  const long long units = (long long)a.B * a.nk, ntiles = (units + 16 / m - 1) / (16 / m);
+  const size_t slot = (size_t)units * m * N;
+  cx<T>* Rws = (cx<T>*)a.R;
+  for (long long tile = (long long)blockIdx.x * nw + wave; tile < ntiles; tile += (long long)gridDim.x * nw) {
+    const GradTile g = grad_tile(tile, lane, N, m, a.Nt, a.k0, a.nk, units);
+    double uj[NU];
+#pragma unroll
+    for (int j = 0; j < NU; ++j) uj[j] = a.u[g.unit * NU + j];
+    const GradXTile x = gradx_tile<NU>(a, tile, lane, g, uj);
+    if (x.nt < 1) continue;  // no counts (never with k_grad_rr_xn's: n_k >= 1): nothing to store
+    const T br = (T)x.mr, bi = (T)x.mi;
+    Own Lam, R, Tn;
+    grad_load<T, NT>((const cx<T>*)a.L, g.bl, g.ok, N, Lam, lane);
+    {
+      const double er = exp(x.mr);
+      const T fr = (T)(er * cos(x.mi)), fi = (T)(-er * sin(x.mi));  // conj(e^{μ_k})
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const auto lr = Lam.r[t], li = Lam.i[t];
+        Lam.r[t] = fr * lr - fi * li;
+        Lam.i[t] = fr * li + fi * lr;
+      }
+    }
+    // b = nt - 1: R(nt) = 0, so R(b) = c_b λ' (+ 0: the value the recurrence below gives from an R(b+1) of zeros)
+    {
+      const int b = x.nt - 1;
+      const T cb = b < x.n ? (T)a.c[b] : T(0);
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        R.r[t] = cb * Lam.r[t] + T(0);
+        R.i[t] = cb * Lam.i[t] + T(0);
+      }
+      grad_store<T, NT>(Rws, (size_t)b * slot + x.wb, g.ok, N, R, lane);
+    }
+#pragma unroll 1
+    for (int b = x.nt - 2; b >= 0; --b) {
+      const T cb = b < x.n ? (T)a.c[b] : T(0);
+      G::template xmul<KS, NU, true>(N, Gr, Gi, uj, R, Tn, lane);
+#pragma unroll
+      for (int t = 0; t < NT; ++t) {
+        const auto rr = R.r[t], ri = R.i[t];
+        R.r[t] = cb * Lam.r[t] + (Tn.r[t] - (br * rr + bi * ri));  // - conj(μ_k) R
+        R.i[t] = cb * Lam.i[t] + (Tn.i[t] - (br * ri - bi * rr));
+      }
+      int ln = lane;
+      asm volatile("" : "+v"(ln));  // opaque per term: otherwise every row offset and mask is hoisted out of the loop and kept
+      grad_store<T, NT>(Rws, (size_t)b * slot + x.wb, g.ok, N, R, ln);
+    }
+  }
+}
+
+// State side and contraction: q_b upward from x_k; per b load R(b), contract into s_j, then q_{b+1} = A_k q_b - μ_k q_b.
+template <typename T, int NT, int KS, int NU>
+__global__ __launch_bounds__(256, 2) void k_grad_rr_xp(const GradXArgs a) {
+  using G = GradRR<T, NT>;
+  using Own = typename G::Own;
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int N = a.N, m = a.m;
+  const int lane = threadIdx.x & 63, wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  const int nw = blockDim.x >> 6;
+  T* Gr = reinterpret_cast<T*>(smem);
+  T* Gi = Gr + (size_t)(NU + 1) * N * G::ldp(N);
+  grad_gens_to_lds<T, NT>(N, NU, (const cx<T>*)a.Agen, Gr, Gi);
+  const long long units = (long long)a.B * a.nk, ntiles = (units + 16 / m - 1) / (16 / m);
+  const size_t slot = (size_t)units * m * N;
+  const cx<T>* Rws = (const cx<T>*)a.R;
+  for (long long tile = (long long)blockIdx.x * nw + wave; tile < ntiles; tile += (long long)gridDim.x * nw) {
+    const GradTile g = grad_tile(tile, lane, N, m, a.Nt, a.k0, a.nk, units);
+    double uj[NU], sj[NU];
+#pragma unroll
+    for (int j = 0; j < NU; ++j) {
+      uj[j] = a.u[g.unit * NU + j];
+      sj[j] = 0.0;
+    }
+    const GradXTile x = gradx_tile<NU>(a, tile, lane, g, uj);
+    const T br = (T)x.mr, bi = (T)x.mi;
+    Own P, Pn, W;
+    grad_load<T, NT>((const cx<T>*)a.X, g.bx, g.ok, N, P, lane);
+#pragma unroll 1
+    for (int b = 0; b < x.nt; ++b) {
+      int ln = lane;
+      asm volatile("" : "+v"(ln));  // opaque per term: otherwise every row offset and mask is hoisted out of the loop and kept
+      grad_load<T, NT>(Rws, (size_t)b * slot + x.wb, g.ok, N, W, ln);
+      G::template contract<KS, NU>(N, Gr, Gi, P, W, sj, lane);
+      if (b + 1 < x.nt) {
+        G::template xmul<KS, NU, false>(N, Gr, Gi, uj, P, Pn, lane);
+#pragma unroll
+        for (int t = 0; t < NT; ++t) {
+          const auto pr = P.r[t], pi = P.i[t];
+          P.r[t] = Pn.r[t] - (br * pr - bi * pi);  // - μ_k q_b
+          P.i[t] = Pn.i[t] - (br * pi + bi * pr);
+        }
+      }
+      asm volatile("" ::: "memory");  // one R(b) in flight: the next load stays behind this term's products
+    }
+    // reduce over the unit's lanes as k_grad_rr_p does: the 4 row groups (l >> 4) and its m columns
+    const int c = lane & 15;
+#pragma unroll
+    for (int j = 0; j < NU; ++j) {
+      double v = sj[j];
       v += __shfl_xor(v, 16);
       v += __shfl_xor(v, 32);
       for (int o = 1; o < m; o <<= 1) v += __shfl_xor(v, o);

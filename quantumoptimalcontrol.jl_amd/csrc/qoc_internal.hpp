@@ -5,7 +5,7 @@
 //   qoc_run.hip           run_forward / run_backward: the propagator chains and the per-slice gradient
 //   qoc_run_expm.hip      the exponential kernels (k_expm, k_expm_rr*)
 //   qoc_run_tchain.hip    the Taylor-action chains (k_tchain_*)
-//   qoc_run_grad.hip      the fused order-3 gradient (k_grad_rr_*)
+//   qoc_run_grad.hip      the fused order-3 gradient and the exact series gradient (k_grad_rr_*)
 //   qoc_run_big.hip       the large-N GEMM pipeline, the GEMM-shaped gradient and the Fréchet gradient
 //   qoc_run_ode.hip       the Tsit5 path
 //   qoc_run_blk.hip       the block chains and block gradient (generators with small invariant blocks), their router
@@ -275,6 +275,12 @@ struct qoc_ctx {
   // exact (Fréchet) gradient mode workspace, allocated on first use
   void* d_fws = nullptr;
   size_t fws_bytes = 0;
+  // the exact gradient as a series on dense generators (qoc_grad_rr.hpp k_grad_rr_x*, qoc_run_grad.hip grad_rr_exact);
+  // its R(b) workspace is d_fws
+  bool exact_series = true;             // QOC_GRAD_EXACT_SERIES=0 at qoc_create: the block exponential everywhere
+  unsigned long long* d_xn = nullptr;   // [0] max n_k, [1] Σ n_k of the last call, then B x Nt term counts (first use)
+  size_t xws_budget = 0;                // workspace budget: min(2 GiB, free / 8) or QOC_GRAD_EXACT_WS_MB (first use)
+  long long xs_stats[4] = {0, 0, 0, 0};  // qoc_exact_series_stats: units, Σ n_k, largest n_k, fallbacks over the cap
   // packed states (compress_states, src/utils.jl:96-109): two parity sectors share the kernels' columns, so the
   // chains and the gradient run on m = max(n1, n2) columns instead of the caller's m_user = n1 + n2
   int m_user = 0;                       // columns of the caller's states (qoc_create's m)
@@ -370,6 +376,10 @@ template <typename T>
 int grad_rr_o3(qoc_ctx* c, double* d_dJdu, hipStream_t st, int k0, int nk, int mode = 0);
 // k_grad_rr_c: the order-3 contraction from the chains' captures (mu_mode: L holds μ, λ = coef ⊙ μ)
 int grad_rr_cap(qoc_ctx* c, double* d_dJdu, hipStream_t st, int k0, int nk, bool mu_mode);
+// QOC_DUKDP_EXACT on dense generators as a series (k_grad_rr_xn / _xq / _xp).  1 (nothing written to d_dJdu): the
+// route does not apply, or the largest term count exceeds GRADX_NMAX: the caller runs frechet_grad
+template <typename T>
+int grad_rr_exact(qoc_ctx* c, double* d_dJdu);
 
 // ---- qoc_run_ode.hip ----
 template <typename T>

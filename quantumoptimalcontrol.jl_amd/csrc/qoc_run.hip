@@ -103,7 +103,7 @@ int run_backward(qoc_ctx* c, int order, double* d_dJdu) {
   return dense_gradient<T>(c, order, d_dJdu);
 }
 
-// the gradient from the stored x_k and λ_k (every chain kind): the exact Fréchet kernel, the fused order-3
+// the gradient from the stored x_k and λ_k (every chain kind): the exact series or Fréchet kernel, the fused order-3
 // kernels, the GEMM-shaped order-3 path or the per-slice k_grad
 template <typename T>
 int dense_gradient(qoc_ctx* c, int order, double* d_dJdu) {
@@ -111,7 +111,8 @@ int dense_gradient(qoc_ctx* c, int order, double* d_dJdu) {
   size_t lds;
   if (order == QOC_DUKDP_EXACT) {
     mk = mark_begin(c, 3);
-    int r = frechet_grad<T>(c, d_dJdu);
+    int r = grad_rr_exact<T>(c, d_dJdu);  // dense contexts the fused kernels fit: the series, no exponential
+    if (r == 1) r = frechet_grad<T>(c, d_dJdu);
     mark_end(c, mk);
     return r;
   }

@@ -134,8 +134,11 @@ end
 
 # grape_sensitivity (src/gradient_computations.jl:35-77) on the GPU; the closure dJfinal_dx is
 # evaluated here at x[end] and handed over as λ_{Nt+1} (QOC_COST_EXTERNAL).  dUkdp_order = 0 (QOC_DUKDP_EXACT) is the
-# exact Fréchet gradient; with this external cost it runs the dense block exponentials (the segmented eval and the
-# interpolating block propagators of blocks of 5..16 rows take it with the built-in costs, qoc_eval_dev).
+# exact Fréchet gradient; with this external cost it runs the dense route (the segmented eval and the interpolating
+# block propagators of blocks of 5..16 rows take it with the built-in costs, qoc_eval_dev): on generators without
+# invariant blocks that the fused gradient kernels fit (N <= 48, m in {1, 2, 4, 8, 16}, nu <= 2) the series kernels,
+# one 16-byte readback of the term counts per call, and the block exponentials when the largest count exceeds 48 or
+# with QOC_GRAD_EXACT_SERIES=0 (read at qoc_create); exact_series_stats(cache) tells which ran.
 function QOC.grape_sensitivity(A0, A::Vector{<:AbstractMatrix}, dJfinal_dx, u, x0, cache::MI355XCache;
                                dUkdp_order=3, dL_dx=nothing)
     # setup_state_penalty's gradient runs on the GPU; nothing clears a penalty left by an earlier call
@@ -159,6 +162,15 @@ function QOC.grape_sensitivity(A0, A::Vector{<:AbstractMatrix}, dJfinal_dx, u, x
     src === nothing || ccall((:qoc_set_costate_source, libqoc), Cint, (Ptr{Cvoid}, Ptr{ComplexF64}), cache.ctx, C_NULL)
     check(rc, cache.ctx)   # QOC_ERR_STALE -> "Cache data from other control signal u"
     return cache.dJdu
+end
+
+"""What the exact gradient's series route did since the last reset (qoc_exact_series_stats): units processed,
+the sum and the largest of their term counts, and the calls that fell back to the block exponential."""
+function exact_series_stats(cache::MI355XCache; reset::Bool=false)
+    v = zeros(Clonglong, 4)
+    check(ccall((:qoc_exact_series_stats, libqoc), Cint, (Ptr{Cvoid}, Ptr{Clonglong}, Cint), cache.ctx, v, reset),
+          cache.ctx)
+    return (units=v[1], terms=v[2], n_max=v[3], fallbacks=v[4])
 end
 
 function set_penalty!(cache::MI355XCache, dL_dx)

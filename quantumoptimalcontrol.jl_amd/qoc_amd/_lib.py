@@ -83,6 +83,7 @@ SIGNATURES = {
     "qoc_allgather_best_dev": (C.c_int, [_vp, _vp]),
     "qoc_set_best_output": (C.c_int, [_vp, _vp]),
     "qoc_chain_terms": (C.c_int, [_vp, C.POINTER(C.c_longlong), C.c_int]),
+    "qoc_exact_series_stats": (C.c_int, [_vp, C.POINTER(C.c_longlong), C.c_int]),
     "qoc_set_spline_basis": (C.c_int, [_vp, _dp, C.c_int]),
     "qoc_eval_spline_dev": (C.c_int, [_vp, C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]),
     "qoc_eval_spline": (C.c_int, [_vp, _dp, C.c_int, _dp, _dp]),

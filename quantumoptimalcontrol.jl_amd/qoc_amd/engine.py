@@ -37,7 +37,10 @@ def _order(order) -> int:
     QOC_BLKSEG_EXACT=0 sends it to the dense Fréchet kernel instead.  On blocks of 5..16 rows with one control (the
     tunable bus) it stays on the interpolating block propagators (info()["backward"] == "blocks_prop16"): the
     derivative of the propagators' own curve in u; QOC_BLKP_EXACT=0, two controls or a control range the interpolation
-    cannot resolve send it to the dense Fréchet kernel, which every other system uses."""
+    cannot resolve send it to the dense Fréchet kernel.  On dense generators (no block path) that the fused gradient
+    kernels fit (fp64, N <= 48, m in {1, 2, 4, 8, 16}, nu <= 2) it is the derivative's series on MFMA, no exponential
+    formed (exact_series_stats() counts it; one 16-byte readback per call; QOC_GRAD_EXACT_SERIES=0, or a slice that
+    needs more than 48 terms, keeps the dense Fréchet kernel), which every other system uses."""
     if isinstance(order, str):
         if order != "exact":
             raise ValueError(f"dUkdp_order must be 1..4 or 'exact' (got {order!r})")
@@ -384,6 +387,15 @@ class GrapeEngine:
         v = C.c_longlong()
         self._chk(self._lib.qoc_chain_terms(self._h, C.byref(v), int(reset)))
         return int(v.value)
+
+    def exact_series_stats(self, reset: bool = False) -> dict:
+        """The exact gradient's series route on dense generators since the last reset (include/qoc.h
+        qoc_exact_series_stats): (seed, slice) units the series kernels processed, the sum and the largest of their
+        term counts n_k, and the calls that ran the block exponential instead because their largest n_k exceeded
+        the cap."""
+        v = (C.c_longlong * 4)()
+        self._chk(self._lib.qoc_exact_series_stats(self._h, v, int(reset)))
+        return {"units": int(v[0]), "terms": int(v[1]), "n_max": int(v[2]), "fallbacks": int(v[3])}
 
     def gemm_stats(self, reset: bool = False) -> dict:
         """Large-N path: live HIP-event time / launches / algorithmic FLOPs of the k_bgemm launches."""

@@ -9,17 +9,28 @@ on
   cavity       N = 40, Nt = 1000, B = 256
   tunable_bus  N = 27, Nt = 2000, B = 512 (blocks of 13 / 14 rows, one control); its exact legs also print the gradient
                kernel's own time per eval (phase "k_grad" of phase_times, a profiled pass after the timed ones).
+  cavity_dense N = 40, Nt = 1000, B = 256 (no invariant blocks: the dense chains and the fused gradient kernels).  Its
+               exact leg is the series on MFMA (k_grad_rr_xn / _xq / _xp), its third leg QOC_GRAD_EXACT_SERIES=0, the
+               block exponentials; the legs on the series also print the gradient phase's own time per eval and the
+               series' counters (exact_series_stats).  Not in the default set: name it.
 Warm-up, then K timed steps between two synchronisations, 3 repeats, every repeat printed, one process at a time.
 A library from before the segmented exact gradient ignores the switch: run from a checkout of that commit, the two exact
 legs both time its dense path (the fourth leg of DESIGN.md's table).
 The dense path is orders of magnitude slower; --dense-steps / --dense-warm shorten the legs that leave the segmented
 path (each step there is long enough to time on its own), the segmented legs always run --steps and the full warm-up.
-Usage: python tools/bench_exact.py [zz|cavity|tunable_bus ...] [--steps K] [--dense-steps K2] [--dense-warm W2]"""
+--tree DIR times the package of another checkout (built there) with this tool: a library from before the dense series
+ignores QOC_GRAD_EXACT_SERIES and has no counters, so its exact legs both time the block exponentials.
+Usage: python tools/bench_exact.py [zz|cavity|tunable_bus|cavity_dense ...] [--steps K] [--dense-steps K2]
+       [--dense-warm W2] [--tree DIR]"""
 import os
 import sys
 import time
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if "--tree" in sys.argv:
+    _i = sys.argv.index("--tree")
+    ROOT = os.path.abspath(sys.argv[_i + 1])
+    del sys.argv[_i:_i + 2]
 sys.path.insert(0, os.path.join(ROOT, "quantumoptimalcontrol.jl_amd"))
 import numpy as np  # noqa: E402
 import torch  # noqa: E402
@@ -49,7 +60,19 @@ def setup(cfg):
 
 
 def fast_path(cfg):  # (the switch that leaves it, what info()["backward"] reports on it)
+    if cfg == "cavity_dense":  # info()["backward"] does not tell the series from the block exponentials: on_fast_path
+        return ("QOC_GRAD_EXACT_SERIES", None)
     return ("QOC_BLKP_EXACT", "blocks_prop16") if cfg == "tunable_bus" else ("QOC_BLKSEG_EXACT", "segmented")
+
+
+def on_fast_path(cfg, eng, order, info):
+    """Whether the step just run stayed off the block exponentials (which get the short --dense-steps legs)."""
+    if cfg != "cavity_dense":
+        return info["backward"] == fast_path(cfg)[1]
+    if order == 3:
+        return True
+    stats = getattr(eng, "exact_series_stats", None)
+    return stats is not None and stats()["units"] > 0
 
 
 def leg(cfg, prob, u, B, order, switch):
@@ -77,7 +100,7 @@ def leg(cfg, prob, u, B, order, switch):
         step()
         eng.synchronize()
         info = eng.info()
-        seg = info["backward"] == fast
+        seg = on_fast_path(cfg, eng, order, info)
         warm, steps = (WARM, K) if seg else (WARM_DENSE, K_DENSE)
         for _ in range(warm - 1):
             step()
@@ -97,7 +120,10 @@ def leg(cfg, prob, u, B, order, switch):
         print(f"{cfg} {form:5s} {tag:32s} backward={info['backward']} split_forward={info['split_forward']} "
               f"steps={steps} J[0]={Jd[0].item():.15g} |g[0]|={gn:.15g} "
               + " ".join(f"{r / 1e6:.6f}" for r in rates) + " M evals/s", flush=True)
-        if cfg == "tunable_bus" and seg:  # the gradient kernel's own time, from events around its launches
+        if cfg == "cavity_dense" and seg and order != 3:
+            print(f"{cfg} {form:5s} {tag:32s} exact_series_stats after {warm + REPEATS * steps} steps: "
+                  f"{eng.exact_series_stats(reset=True)}", flush=True)
+        if cfg in ("tunable_bus", "cavity_dense") and seg:  # the gradient kernel's own time, from events around its launches
             eng.set_profiling(True)
             eng.phase_times(reset=True)
             for _ in range(10):
