@@ -324,12 +324,25 @@ RcclApi& rccl() {
   return api;
 }
 
+// Every forward begins here (forward, qoc_eval_dev, qoc_propagate_envelope): x_k and J are about to be rewritten, so the
+// plain records; the path that runs fills in what it leaves
+static void forward_begin(qoc_ctx* c) {
+  c->fwd = {};
+  c->jbest = {};
+}
+// and ends here: the states are this u's; the host copies for the stale check are the caller's to fill (unknown for a
+// device-side u)
+static int forward_done(qoc_ctx* c) {
+  c->fwd.valid = true;
+  c->h_u.clear();
+  c->h_coef.clear();
+  return QOC_OK;
+}
+
 // d_src: the caller's device u when it is not yet in d_u (the segmented forward copies it itself), d_J: the caller's J
 // buffer (written by that launch; the other paths leave J in d_J)
 int forward(qoc_ctx* c, const double* d_src = nullptr, double* d_J = nullptr) {
-  c->X_lazy = false;  // every forward path but the segmented one writes x_k
-  c->best_ready = false;
-  c->fwd_kind = 0;
+  forward_begin(c);
   if (blkseg_split_ok(c)) return blkseg_forward(c, d_src ? d_src : c->d_u, d_J);
   if (d_src && d_src != c->d_u)
     HIPCHK(c, hipMemcpyAsync(c->d_u, d_src, (size_t)c->B * c->nu * c->Nt * sizeof(double), hipMemcpyDeviceToDevice,
@@ -347,7 +360,8 @@ int wait_stale_check(qoc_ctx* c);
 int backward(qoc_ctx* c, int order, double* d_dJdu, const int* stale = nullptr) {
   // the segmented forward left G at every segment's end: the backward half only (x_k never formed); the stored block
   // propagators: the μ recurrence and the gradient on them
-  if (c->fwd_kind == 1 && blkseg_ok(c, order)) return blkseg_backward(c, order, d_dJdu, stale);
+  // (both before bwd is reset: on a stale u they write nothing, and the last backward's record stands)
+  if (c->fwd.kind == 1 && blkseg_ok(c, order)) return blkseg_backward(c, order, d_dJdu, stale);
   if (blkp_backward_ok(c, order)) {
     const int r = blkp_backward(c, order, d_dJdu, stale);
     if (r != 1) return r;
@@ -357,13 +371,11 @@ int backward(qoc_ctx* c, int order, double* d_dJdu, const int* stale = nullptr) 
       if (const int w = wait_stale_check(c)) return w;
   }
   if (c->cost_kind == QOC_COST_EXTERNAL || c->src_on) c->dead_dirty = true;  // λ may be nonzero on dead rows
-  if (c->X_lazy) {  // after a segmented eval: the backward paths read x_k
+  if (c->fwd.lazy) {  // after a segmented eval: the backward paths read x_k
     const int r = blku_states(c);
     if (r) return r;
   }
-  c->L_is_mu = false;  // every backward path below writes λ itself (the fused block backward: on demand)
-  c->L_lazy = false;
-  c->last_eval_mode = 0;
+  c->bwd = {};  // every backward path below writes λ itself (the fused block backward: on demand)
   if (c->src_on && c->prop_method == QOC_PROP_TSIT5)
     return fail(c, QOC_ERR_UNSUPPORTED, "a co-state source (dL_dx) is not part of the Tsit5 path (compute_pwc_gradient)");
   if (blk_active(c)) return blk_backward(c, order, d_dJdu);
@@ -748,15 +760,17 @@ int qoc_set_generators(qoc_ctx* c, const double* A0, const double* const* Aj) {
   }
   if (c->tchain_ok) {  // invariant blocks of the generators (qoc_blk.hpp)
     c->int_ok = c->int_failed = false;  // the interpolated propagators belong to the old generators
-    c->ichain_fwd = false;
-    c->fwd_kind = 0;  // a split forward's propagators or coefficients belong to the old generators
+    // the model's row "set_generators: fwd cleared": beyond the states (valid, below), a split forward's propagators or
+    // coefficients belong to the old generators
+    c->fwd.kind = 0;
+    c->fwd.ichain = false;
     r = blk_detect(c);
     if (r) return r;
   } else {
     c->blk_nb = 0;
   }
   c->have_gen = true;
-  c->have_prop = false;
+  c->fwd.valid = false;
   return QOC_OK;
 }
 
@@ -772,7 +786,7 @@ int qoc_set_x0(qoc_ctx* c, const double* x0, int per_seed) {
   c->x0_per_seed = per_seed ? 1 : 0;
   c->dead_dirty = true;  // rows live under the previous x0 may hold nonzero states
   c->have_x0 = true;
-  c->have_prop = false;
+  c->fwd.valid = false;
   return QOC_OK;
 }
 
@@ -798,7 +812,7 @@ int qoc_set_cost(qoc_ctx* c, int kind, const double* X_target, double n) {
   c->cost_n = n;
   c->dead_dirty = true;  // rows live under the previous target may hold nonzero co-states
   c->have_cost = true;
-  c->have_prop = false;
+  c->fwd.valid = false;
   return QOC_OK;
 }
 
@@ -820,9 +834,10 @@ int qoc_set_state_penalty(qoc_ctx* c, const int* P, int np, const int* C, int nc
   c->h_pen_rows.assign(P, P + np);
   c->h_pen_cols.assign(C, C + nc);
   // what the segmented eval keeps of the penalty: its row / column masks (and with them the shape key), and the G and
-  // D a split forward stored at the segment ends, which carry the old penalty (the backward then rebuilds x_k)
+  // D a split forward stored at the segment ends, which carry the old penalty (the backward then rebuilds x_k): the
+  // model's row "set_state_penalty: fwd kept", a later sensitivity on fwd's states with the current penalty
   c->seg_pen_valid = false;
-  if (c->fwd_kind == 1) c->fwd_kind = 0;
+  if (c->fwd.kind == 1) c->fwd.kind = 0;
   // kernels queued by the asynchronous entry points may still read the mask: finish them first (the engine
   // stream is non-blocking, a null-stream copy would not wait for it)
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -948,7 +963,7 @@ int qoc_set_compression(qoc_ctx* c, const int* rows1, int nr1, const int* cols1,
     HIPCHK(c, hipMalloc(&c->d_gws, bytes));
     c->dev_bytes += bytes;
   }
-  c->have_prop = false;
+  c->fwd.valid = false;
   return QOC_OK;
 }
 
@@ -957,17 +972,13 @@ int qoc_propagate_dev(qoc_ctx* c, const double* d_u, double* d_J) {
   if (r) return r;
   if (!d_u) return fail(c, QOC_ERR_ARG, "d_u is null");
   r = forward(c, d_u, d_J);  // u into d_u (kept for the stale check), J into d_J and the caller's buffer
-  if (r) return r;
-  c->have_prop = true;
-  c->h_u.clear();  // host copy unknown for device-side u
-  c->h_coef.clear();
-  return QOC_OK;
+  return r ? r : forward_done(c);
 }
 
 int qoc_grape_sensitivity_dev(qoc_ctx* c, const double* d_u, int order, double* d_dJdu) {
   int r = check_ready(c);
   if (r) return r;
-  if (!c->have_prop) return fail(c, QOC_ERR_STATE, "grape_sensitivity called before propagate");
+  if (!c->fwd.valid) return fail(c, QOC_ERR_STATE, "grape_sensitivity called before propagate");
   if (order < 0 || order > 4) return fail(c, QOC_ERR_ARG, "dUkdp_order must be 1..4 or QOC_DUKDP_EXACT (got %d)", order);
   if (c->cost_kind == QOC_COST_EXTERNAL)
     return fail(c, QOC_ERR_STATE, "QOC_COST_EXTERNAL needs qoc_grape_sensitivity (host lambda_final)");
@@ -975,18 +986,13 @@ int qoc_grape_sensitivity_dev(qoc_ctx* c, const double* d_u, int order, double* 
   if (!d_u || d_u == c->d_u) return backward(c, order, out);  // the cache's own u (the reference passes cache.u)
   const int* dflag = nullptr;
   if ((r = queue_stale_check(c, d_u, &dflag))) return r;
-  if ((c->fwd_kind == 1 && blkseg_ok(c, order)) || blkp_backward_ok(c, order)) {
+  if ((c->fwd.kind == 1 && blkseg_ok(c, order)) || blkp_backward_ok(c, order)) {
     // the split backward's launches read the flag themselves and write nothing on a stale u: they are queued behind
     // the check, and the host waits for the check alone, not for them (the stream never idles between the calls)
-    const bool lmu = c->L_is_mu, llazy = c->L_lazy;
-    const int lmode = c->last_eval_mode;
+    const LastBwd last = c->bwd;
     r = backward(c, order, out, dflag);
     const int w = wait_stale_check(c);
-    if (w) {  // nothing was written: the co-states are still the last grape_sensitivity's
-      c->L_is_mu = lmu;
-      c->L_lazy = llazy;
-      c->last_eval_mode = lmode;
-    }
+    if (w) c->bwd = last;  // nothing was written: the co-states are still the last grape_sensitivity's
     return w ? w : r;
   }
   if ((r = wait_stale_check(c))) return r;
@@ -996,53 +1002,41 @@ int qoc_grape_sensitivity_dev(qoc_ctx* c, const double* d_u, int order, double* 
 int qoc_eval_dev(qoc_ctx* c, const double* d_u, int order, double* d_J, double* d_dJdu) {
   if (c && c->cost_kind == QOC_COST_EXTERNAL)
     return fail(c, QOC_ERR_STATE, "qoc_eval_dev needs a device-side cost (TRACE or ZCAL)");
-  if (c) c->fwd_kind = 0;  // whatever runs below leaves no split forward behind
-  if (c && c->have_gen && c->concurrent && blkseg_ok(c, order)) {
+  int r = check_ready(c);
+  if (r) return r;
+  if (!d_u) return fail(c, QOC_ERR_ARG, "d_u is null");
+  double* const out = d_dJdu ? d_dJdu : c->d_dJdu;
+  if (c->concurrent && blkseg_ok(c, order)) {
     // block propagators with the time axis in segments: one launch reads u (and copies it to d_u) and writes J and
     // dJdu; x_k and λ_k are rebuilt on demand (qoc_blkseg.hpp)
-    int r = check_ready(c);
-    if (r) return r;
-    if (!d_u) return fail(c, QOC_ERR_ARG, "d_u is null");
-    c->have_prop = false;
-    r = blkseg_eval(c, order, d_u, d_J, d_dJdu ? d_dJdu : c->d_dJdu);
-    if (r) return r;
+    forward_begin(c);
+    c->bwd = {};
+    if ((r = blkseg_eval(c, order, d_u, d_J, out))) return r;
     c->props_since_reset++;
-    c->have_prop = true;
-    c->h_u.clear();
-    c->h_coef.clear();
-    return QOC_OK;
+    return forward_done(c);
   }
-  if (c) {
-    c->X_lazy = false;  // the other eval paths write x_k
-    c->best_ready = false;
-  }
-  if (c && c->have_gen && (blk_concurrent_ok(c, order) || tchain_concurrent_ok(c, order))) {
+  if (blk_concurrent_ok(c, order) || tchain_concurrent_ok(c, order)) {
     // forward chain and the μ recurrence side by side (tchain_eval_concurrent)
-    int r = check_ready(c);
-    if (r) return r;
-    if (!d_u) return fail(c, QOC_ERR_ARG, "d_u is null");
     const size_t nu_t = (size_t)c->B * c->nu * c->Nt;
     if (d_u != c->d_u) HIPCHK(c, hipMemcpyAsync(c->d_u, d_u, nu_t * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-    c->have_prop = false;
-    c->L_lazy = false;
-    r = blk_concurrent_ok(c, order)  ? blk_eval_concurrent(c, order, d_dJdu ? d_dJdu : c->d_dJdu)
-        : c->prec == QOC_FP64 ? tchain_eval_concurrent<double>(c, d_dJdu ? d_dJdu : c->d_dJdu)
-                              : tchain_eval_concurrent<float>(c, d_dJdu ? d_dJdu : c->d_dJdu);
+    forward_begin(c);
+    c->bwd = {};
+    r = blk_concurrent_ok(c, order) ? blk_eval_concurrent(c, order, out)
+        : c->prec == QOC_FP64       ? tchain_eval_concurrent<double>(c, out)
+                                    : tchain_eval_concurrent<float>(c, out);
     if (r != 1) {  // (1: an exact eval off the interpolating block propagators, nothing launched: the calls below)
       if (r) return r;
       c->props_since_reset++;
       if (d_J && d_J != c->d_J)
         HIPCHK(c, hipMemcpyAsync(d_J, c->d_J, c->B * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-      c->have_prop = true;
-      c->h_u.clear();
-      c->h_coef.clear();
-      return QOC_OK;
+      return forward_done(c);
     }
   }
-  int r = qoc_propagate_dev(c, d_u, d_J);
-  if (r) return r;
+  // propagate, then the backward (which takes a split forward's leftovers where the propagate left some)
+  if ((r = forward(c, d_u, d_J))) return r;
+  forward_done(c);
   if (order < 0 || order > 4) return fail(c, QOC_ERR_ARG, "dUkdp_order must be 1..4 or QOC_DUKDP_EXACT (got %d)", order);
-  return backward(c, order, d_dJdu ? d_dJdu : c->d_dJdu);
+  return backward(c, order, out);
 }
 
 int qoc_propagate(qoc_ctx* c, const double* u, double* J_out) {
@@ -1055,16 +1049,15 @@ int qoc_propagate(qoc_ctx* c, const double* u, double* J_out) {
   if (r) return r;
   if (J_out) HIPCHK(c, hipMemcpyAsync(J_out, c->d_J, c->B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
+  forward_done(c);
   c->h_u.assign(u, u + nu_t);
-  c->h_coef.clear();
-  c->have_prop = true;
   return QOC_OK;
 }
 
 int qoc_grape_sensitivity(qoc_ctx* c, const double* u, int order, const double* lambda_final, double* dJdu_out) {
   int r = check_ready(c);
   if (r) return r;
-  if (!c->have_prop) return fail(c, QOC_ERR_STATE, "grape_sensitivity called before propagate");
+  if (!c->fwd.valid) return fail(c, QOC_ERR_STATE, "grape_sensitivity called before propagate");
   if (order < 0 || order > 4) return fail(c, QOC_ERR_ARG, "dUkdp_order must be 1..4 or QOC_DUKDP_EXACT (got %d)", order);
   const size_t nu_t = (size_t)c->B * c->nu * c->Nt;
   if (!u) return fail(c, QOC_ERR_ARG, "u is null");
@@ -1097,11 +1090,11 @@ int qoc_grape_sensitivity(qoc_ctx* c, const double* u, int order, const double* 
 
 int qoc_get_states(qoc_ctx* c, int seed, int k, double* x_out) {
   if (!c || !x_out) return fail(c, QOC_ERR_ARG, "null argument");
-  if (!c->have_prop) return fail(c, QOC_ERR_STATE, "no propagated states");
+  if (!c->fwd.valid) return fail(c, QOC_ERR_STATE, "no propagated states");
   if (k == -1) k = c->Nt;
   if (seed < 0 || seed >= c->B || k < 0 || k > c->Nt) return fail(c, QOC_ERR_ARG, "index out of range");
   HIPCHK(c, hipSetDevice(c->dev));
-  if (c->X_lazy) {  // after a segmented eval: the states are rebuilt on demand
+  if (c->fwd.lazy) {  // after a segmented eval: the states are rebuilt on demand
     const int r = blku_states(c);
     if (r) return r;
   }
@@ -1116,11 +1109,11 @@ int qoc_get_costates(qoc_ctx* c, int seed, int k, double* lam_out) {
   HIPCHK(c, hipSetDevice(c->dev));
   const size_t Nm = (size_t)c->N * c->m;
   const void* src = (char*)c->d_L + ((size_t)seed * (c->Nt + 1) + k) * Nm * c->esz;
-  if (c->L_lazy) {
+  if (c->bwd.lazy) {
     const int r = blku_costates(c);
     if (r) return r;
   }
-  if (!c->L_is_mu) return download_states(c, src, lam_out);
+  if (!c->bwd.is_mu) return download_states(c, src, lam_out);
   // the concurrent eval left μ_k: λ_k = coef ⊙ μ_k (per row sector and packed column, lam_coef)
   std::vector<double> mu(2 * Nm), cf(4 * (size_t)c->m);
   int r = download(c, src, mu.data(), Nm);
@@ -1146,7 +1139,7 @@ int qoc_get_costates(qoc_ctx* c, int seed, int k, double* lam_out) {
 
 int qoc_get_propagator(qoc_ctx* c, int seed, int k, double* U_out) {
   if (!c || !U_out) return fail(c, QOC_ERR_ARG, "null argument");
-  if (!c->have_prop) return fail(c, QOC_ERR_STATE, "no propagators");
+  if (!c->fwd.valid) return fail(c, QOC_ERR_STATE, "no propagators");
   if (c->prop_method == QOC_PROP_TSIT5) return fail(c, QOC_ERR_STATE, "the Tsit5 path does not form propagators");
   if (seed < 0 || seed >= c->B || k < 0 || k >= c->Nt) return fail(c, QOC_ERR_ARG, "index out of range");
   HIPCHK(c, hipSetDevice(c->dev));
@@ -1305,7 +1298,7 @@ int qoc_sensitivity_spline(qoc_ctx* c, const double* coef, int order, double* dJ
   int r = check_ready(c);
   if (r) return r;
   const size_t nc = (size_t)c->B * c->ns * c->nu;
-  if (!c->have_prop || c->h_coef.size() != nc || std::memcmp(coef, c->h_coef.data(), nc * sizeof(double)) != 0)
+  if (!c->fwd.valid || c->h_coef.size() != nc || std::memcmp(coef, c->h_coef.data(), nc * sizeof(double)) != 0)
     return fail(c, QOC_ERR_STALE, "Cache data from other control signal u");
   if (order < 0 || order > 4) return fail(c, QOC_ERR_ARG, "dUkdp_order must be 1..4 or QOC_DUKDP_EXACT (got %d)", order);
   if (c->cost_kind == QOC_COST_EXTERNAL)
@@ -1345,7 +1338,7 @@ int qoc_set_propagation(qoc_ctx* c, int method, int nsub) {
     c->nsub = nsub;
   }
   c->prop_method = method;
-  c->have_prop = false;
+  c->fwd.valid = false;
   return QOC_OK;
 }
 
@@ -1365,8 +1358,8 @@ int qoc_propagate_envelope(qoc_ctx* c, int kind, const double* params, int np, d
   double* dP = nullptr;
   HIPCHK(c, hipMalloc((void**)&dP, (size_t)c->B * np * sizeof(double)));
   hipError_t e = hipMemcpy(dP, params, (size_t)c->B * np * sizeof(double), hipMemcpyHostToDevice);
+  forward_begin(c);  // J and x(tgate) are rewritten below; states other than x(tgate) are not stored: fwd stays invalid
   if (e == hipSuccess) e = launch_envelope(c, kind, dP, np, dt, nsteps);
-  c->best_ready = false;  // J is rewritten below
   if (e == hipSuccess && c->cost_kind != QOC_COST_EXTERNAL) e = launch_terminal_cost(c);
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e == hipSuccess && J_out && c->cost_kind != QOC_COST_EXTERNAL)
@@ -1380,7 +1373,6 @@ int qoc_propagate_envelope(qoc_ctx* c, int kind, const double* params, int np, d
     }
   }
   if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "qoc_propagate_envelope: %s", hipGetErrorString(e));
-  c->have_prop = false;  // states other than x(tgate) are not stored
   return QOC_OK;
 }
 
@@ -1400,13 +1392,13 @@ int qoc_get_info(qoc_ctx* c, long long* info) {
   info[5] = c->big ? c->expm_alg : c->expm_run;  // the large-N pipeline keeps its own (Taylor / Padé) choice
   info[6] = c->chain_mode == 1 && c->cheb && tchain_mf(c) ? 1 : 0;  // Taylor-action chains: Chebyshev terms
   info[7] = c->m;  // state columns the kernels run on (< the caller's m when compress_states packing is on)
-  info[8] = c->last_eval_mode;  // last backward: 0 other, 1 captured products, 2 / 3 / 4 concurrent μ recurrence, 5 fused block gradient, 6 segmented block eval, 7 stored propagators of blocks of 5..16 rows
-  info[9] = c->fwd_captured ? 1 : 0;
+  info[8] = c->bwd.route;  // last backward: 0 other, 1 captured products, 2 / 3 / 4 concurrent μ recurrence, 5 fused block gradient, 6 segmented block eval, 7 stored propagators of blocks of 5..16 rows
+  info[9] = c->fwd.captured ? 1 : 0;
   // 6: the last eval ran the stored-propagator chains of blocks of 5..16 rows (propagate / grape_sensitivity: 4)
-  info[11] = c->fwd_kind;
-  info[13] = c->ichain_last;  // the last eval / propagate on blocks of 5..16 rows: interpolating chains (2: triangle)
-  info[12] = c->last_int_D;  // the stored block propagators' last formation: interpolation degree in u (0: exponentials)
-  info[10] = blk_active(c) ? (blku_on(c) ? 5 : blkp_on(c) && c->last_eval_mode == 7 ? 6 : blk_rot(c) ? 4 : 3) : c->big || c->chain_mode != 1 || !tchain_mf(c) ? 0 : tchain_mf_rot(c) ? 2 : 1;
+  info[11] = c->fwd.kind;
+  info[13] = c->fwd.formed_ichain;  // the last eval / propagate on blocks of 5..16 rows: interpolating chains (2: triangle)
+  info[12] = c->fwd.formed_D;  // the stored block propagators' last formation: interpolation degree in u (0: exponentials)
+  info[10] = blk_active(c) ? (blku_on(c) ? 5 : blkp_on(c) && c->bwd.route == 7 ? 6 : blk_rot(c) ? 4 : 3) : c->big || c->chain_mode != 1 || !tchain_mf(c) ? 0 : tchain_mf_rot(c) ? 2 : 1;
   return QOC_OK;
 }
 
@@ -1423,7 +1415,7 @@ int qoc_set_chain(qoc_ctx* c, int mode) {
     mode = c->tchain_ok && c->have_gen &&
                    (c->cheb && tchain_mf(c) ? c->tprm.rad[0] <= 25.0 : c->tprm.nrm[0] <= 1.0) ? 1 : 0;
   c->chain_mode = mode;
-  c->have_prop = false;
+  c->fwd.valid = false;
   return QOC_OK;
 }
 
@@ -1451,7 +1443,7 @@ int qoc_comm_init(qoc_ctx* c, int world, int rank, const void* id, long long see
   }
   if (c->d_best) HIPCHK(c, hipFree(c->d_best));
   c->d_best = nullptr;
-  c->best_ready = false;
+  c->jbest = {};  // the gathered slot goes with the buffer
   c->world = 1;
   c->rank = 0;
   c->seed_offset = 0;
@@ -1497,9 +1489,9 @@ int qoc_allgather_best_dev(qoc_ctx* c, double* d_out) {
   double* res = c->d_best + 2 + 2 * c->world;
   double* slot = c->d_best + 2 + 2 * c->rank;  // this rank's pair in the gathered array (in-place all-gather)
   // one rank, and the eval already wrote the final pair into res and the registered output: nothing to queue
-  if (c->best_ready && c->best_direct && c->world == 1 && (d_out == nullptr || d_out == c->best_out)) return QOC_OK;
-  // the segmented eval already reduced its J in its last workgroup (best_ready); otherwise k_argmin_seed
-  if (!c->best_ready) {
+  if (c->jbest.ready && c->jbest.direct && c->world == 1 && (d_out == nullptr || d_out == c->best_out)) return QOC_OK;
+  // the segmented eval already reduced its J in its last workgroup (jbest.ready); otherwise k_argmin_seed
+  if (!c->jbest.ready) {
     hipLaunchKernelGGL(k_argmin_seed, dim3(1), dim3(256), 0, c->stream, (const double*)c->d_J, c->B, c->seed_offset,
                        slot);
     HIPCHK(c, hipGetLastError());
@@ -1518,7 +1510,7 @@ int qoc_allgather_best_dev(qoc_ctx* c, double* d_out) {
 int qoc_set_best_output(qoc_ctx* c, double* d_out) {
   if (!c) return fail(nullptr, QOC_ERR_ARG, "null context");
   c->best_out = d_out;
-  c->best_direct = false;  // the next eval decides
+  c->jbest.direct = false;  // the next eval decides
   return QOC_OK;
 }
 

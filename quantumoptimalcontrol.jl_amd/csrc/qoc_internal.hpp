@@ -44,6 +44,54 @@ struct BlksegShape {
   size_t lds;
 };
 
+// The last successful forward (propagate / eval).  Plain: x_k of the u in d_u are in d_X and nothing else is kept.
+struct LastFwd {
+  // The states (or what rebuilds them) are there.  A setter that changes the system (the model's "cleared") clears this
+  // member alone, after blk_materialize: every reader of the others asks for it first, and qoc_get_info goes on
+  // reporting the dropped forward's kind, captures and formation until the next forward's reset.
+  bool valid = false;
+  // what a propagate left for grape_sensitivity (the reference's split call form, examples/ipopt_callbacks_exp.jl:
+  // 11-31): 0 states in d_X (every path), 1 the segmented forward's G at every segment end (d_gseg, qoc_blkseg.hpp
+  // BLKSEG_FWD), 2 the stored block propagators and states of blocks of 5..16 rows (d_blkU + d_X, qoc_blkp.hpp; or the
+  // interpolating chains' states alone, ichain)
+  int kind = 0;
+  // the segmented block eval (qoc_blkseg.hpp) writes neither x_k nor λ_k: qoc_get_states / a later backward rebuild
+  // the states on demand (blku_states) from the u in d_u, with J and the coefficients going to scratch
+  bool lazy = false;
+  bool captured = false;  // the Taylor-action chain wrote its captures (d_pws)
+  // kind 2, blkp_forward's leftovers: it ran the interpolating chains (k_blkp_ichain, no stored propagators:
+  // grape_sensitivity's μ recurrence interpolates from the same coefficients); the wave blocks it ran on (the live
+  // ones, or all with a co-state source); its propagators were interpolated (the exact backward needs N_i).
+  // blkp_backward rewrites the first two when it forms the propagators of another layout.
+  bool ichain = false;
+  int nwb = 0;
+  bool interp = false;
+  // The step records in d_steps.  They describe that buffer rather than the forward, and a backward's re-prep
+  // (blk_backward) rewrites them; they are here because only a forward makes them stale: every path that reads the
+  // records preps in its own forward, except after one on propagators formed without them (blkp), which says so.
+  bool steps_old = false;  // not this u's: re-prep first
+  bool steps_cheb = false;   // what tchain_prep wrote: Chebyshev coefficients (the backward pass reuses its steps)
+  // report only (qoc_get_info), of the last block-propagator formation: the degree it was planned with (blkp_plan; 0:
+  // exponentials) and the chains that ran on it (0: stored, 1: interpolating, every entry, 2: the symmetric
+  // propagators' upper triangle; blkp_backward writes 0 when it re-forms)
+  int formed_D = 0;
+  int formed_ichain = 0;
+};
+// The last successful backward (grape_sensitivity / eval).  Plain: λ_k in d_L.
+struct LastBwd {
+  bool is_mu = false;  // d_L holds μ_k (qoc_get_costates applies the coefficients d_coef_mu)
+  bool lazy = false;   // the fused block backward left d_L unwritten: qoc_get_costates rebuilds it (blku_costates)
+                       // from the saved u and λ_N coefficients (d_u_lam, d_coef_lam)
+  int route = 0;       // qoc_get_info: 0 other, 1 captured sequential backward, 2 / 3 concurrent μ mode on two streams /
+                       // in one dual launch, 4 block chains, 5 fused block gradient, 6 segmented block eval, 7 stored
+                       // propagators of blocks of 5..16 rows
+};
+// The forward whose J is in d_J, for qoc_allgather_best (the setters leave it).  Plain: k_argmin_seed finds the pair.
+struct LastJ {
+  bool ready = false;   // the eval already wrote this rank's best (J, seed) into the gathered slot
+  bool direct = false;  // and the final pair into the result slot and best_out
+};
+
 struct qoc_ctx {
   int dev = 0, N = 0, m = 0, nu = 0, Nt = 0, B = 0, prec = QOC_FP64;
   size_t esz = 16;  // bytes per complex element on device
@@ -147,14 +195,11 @@ struct qoc_ctx {
   TChainParams tprm{};
   bool cheb_ok = false;          // generators skew-Hermitian with imaginary shifts: Chebyshev applies
   bool cheb = false;             // Chebyshev terms (k_tchain_prep_cheb) instead of Taylor (QOC_TCHAIN_POLY=taylor)
-  bool cheb_ran = false;         // what the last forward pass used (the backward pass reuses its steps)
-  bool steps_stale = false;      // the last eval formed its propagators without step records (blkp): re-prep first
   double* d_tcoef = nullptr;     // B x Nt x TCHEB_STRIDE Chebyshev coefficients (allocated on first use)
   long long props_since_reset = 0;  // forward passes since the last Padé-histogram reset (chain mode 1)
   // Captured products (register-resident MFMA chains, order-3 fused gradient): the chains write their first two
   // products per slice (forward -> d_pws, backward -> d_gws) and the gradient is k_grad_rr_c, contractions only.
   bool cap_ok = false;           // the shape takes it (qoc_set_generators; QOC_CAPTURE=0 turns it off)
-  bool fwd_captured = false;     // the last forward pass wrote its captures
   // qoc_eval_dev with a built-in cost and no penalty / co-state source: the backward recurrence runs from X_target
   // (μ_k, λ_k = coef ⊙ μ_k) beside the forward chain: 1 (default) both in one launch (k_tchain_mf_dual), 2 two
   // launches on two streams, 0 off (QOC_CONCURRENT)
@@ -162,10 +207,7 @@ struct qoc_ctx {
   // the MFMA chains with the state in registers (TChainRot): 1 (default) for N <= 32 with nu <= 2, 3 also for
   // N <= 48 (generators in LDS), 0 off: TChainMF everywhere (QOC_TCHAIN_ROT)
   int tchain_rot = 1;
-  bool L_is_mu = false;          // d_L holds μ_k (qoc_get_costates applies the coefficients d_coef_mu)
-  bool L_lazy = false;           // the fused block backward left d_L unwritten: qoc_get_costates rebuilds it
-                                 // (blku_costates) from the saved u and λ_N coefficients
-  double* d_u_lam = nullptr;     // B x Nt x nu: u of that backward
+  double* d_u_lam = nullptr;     // B x Nt x nu: u of the backward that left λ_k to be rebuilt (bwd.lazy)
   void* d_blkU = nullptr;        // B x Nt x NB^2 x nblk complex: block propagators of the eval's forward (fused backward)
   size_t blkU_bytes = 0;         // its allocated size (reallocated when a new block layout needs more)
   // one control: the propagators interpolated in u (qoc_blkp.hpp k_blkp_int): the coefficient matrices of the control
@@ -185,33 +227,16 @@ struct qoc_ctx {
   int int_E = 0;
   std::vector<int> int_Eb;
   size_t int_noff = 0, int_nsoff = 0;
-  bool blkp_fwd_interp = false;      // blkp_forward's propagators were interpolated (the exact backward needs N_i)
   bool int_failed = false;           // [int_fail_lo, int_fail_hi] did not converge (a wider range will not either)
   double int_fail_lo = 0.0, int_fail_hi = 0.0;
   double* d_minmax = nullptr;        // k_minmax partials (256 blocks x 2)
   double* h_minmax = nullptr;        // pinned host copy
-  int last_int_D = 0;                // the degree the last formation ran with (0: not interpolated; qoc_get_info)
-  // the last eval / propagate ran the interpolating chains (k_blkp_ichain: no stored propagators); for the split call
-  // form: grape_sensitivity's μ recurrence interpolates from the same coefficients (set by blkp_forward, cleared by
-  // every other forward and by new generators)
   double2* d_blkp_ph = nullptr;      // B x Nt: e^{μ(u_k)} for the interpolating chains (k_blkp_phase)
   size_t blkp_ph_n = 0;
-  int ichain_last = 0;               // 0: no, 1: every entry, 2: the symmetric propagators' upper triangle
-  bool ichain_fwd = false;
-  int blkp_fwd_nwb = 0;              // the wave blocks blkp_forward ran on (the live ones, or all with a co-state source)
   double* d_blkp_ctab = nullptr; // the Chebyshev form's coefficient table (qoc_blkp.hpp blkp_cheb), for ctab_cm / ctab_rmax
   int ctab_cm = 0;
   double ctab_rmax = 0.0;
-  // the segmented block eval (qoc_blkseg.hpp) writes neither x_k nor λ_k: qoc_get_states / a later backward rebuild
-  // the states on demand (blku_states) from the u in d_u, with J and the coefficients going to scratch
-  bool X_lazy = false;
-  // what the last propagate left for grape_sensitivity (the reference's split call form,
-  // examples/ipopt_callbacks_exp.jl:11-31): 0 states in d_X (every path), 1 the segmented forward's G at every
-  // segment end (d_gseg, qoc_blkseg.hpp BLKSEG_FWD), 2 the stored block propagators and states of blocks of 5..16 rows
-  // (d_blkU + d_X, qoc_blkp.hpp; or the interpolating chains' states alone, ichain_fwd).  Reset by every other
-  // forward or eval.
-  int fwd_kind = 0;
-  double2* d_gseg = nullptr;         // B x NB^2 x S x nblk complex
+  double2* d_gseg = nullptr;         // B x NB^2 x S x nblk complex: the segmented forward's G at every segment end (fwd.kind 1)
   size_t gseg_bytes = 0;
   // the segmented eval's launch shape, kept between evals: valid while the sizes it was derived from (seg_key: B, Nt,
   // N, m, nu, block rows, blocks, penalised or not) are the context's; the QOC_BLKSEG_W / _S / _RB switches are read
@@ -236,8 +261,6 @@ struct qoc_ctx {
   bool skew_exact = false;
   cx<double>* d_coef_lam = nullptr;  // B x 2m: its λ_N coefficients
   cx<double>* d_coef_mu = nullptr;  // B x 2m: the λ_N coefficients of the eval that left μ in d_L
-  int last_eval_mode = 0;        // 0 other, 1 captured sequential backward, 2 / 3 concurrent μ mode: two streams /
-                                 // one dual launch, 4 block chains' concurrent eval (qoc_get_info)
   // generators with small invariant blocks (qoc_blk.hpp, detected at qoc_set_generators; QOC_BLOCKS=0 off): the
   // chains and the gradient run per block
   int blk_nb = 0;                // padded block size 2 / 3 / 4 (VALU lanes), 16 (MFMA block waves), 0: no block path
@@ -270,8 +293,6 @@ struct qoc_ctx {
   double* d_best = nullptr;    // [2 local | 2 x world gathered | 2 result]
   unsigned int* d_done = nullptr;  // the segmented eval's workgroup counter (its last workgroup finds the best pair)
   double* best_out = nullptr;  // qoc_set_best_output's buffer
-  bool best_direct = false;     // the last eval also wrote the final pair into the result slot and best_out
-  bool best_ready = false;     // the last eval already wrote this rank's best (J, seed) into the gathered slot
   // exact (Fréchet) gradient mode workspace, allocated on first use
   void* d_fws = nullptr;
   size_t fws_bytes = 0;
@@ -294,7 +315,13 @@ struct qoc_ctx {
   // caller-layout copies, re-packed when the packing changes
   std::vector<double> h_gen, h_x0, h_Xt;
   std::vector<int> h_pen_rows, h_pen_cols;
-  bool have_gen = false, have_x0 = false, have_cost = false, have_prop = false;
+  bool have_gen = false, have_x0 = false, have_cost = false;
+  // What the last calls left: the three snapshots of the model in tests/engine_model.py (its table lists, per call, what
+  // happens to each).  A forward, an eval and a backward assign the plain record first (c->fwd = {}, c->bwd = {}); a
+  // path then writes the members it leaves different, after the launch that makes them so.
+  LastFwd fwd;    // the model's fwd
+  LastBwd bwd;    // the model's bwd
+  LastJ jbest;    // the model's jfwd
   std::string err;
 };
 
@@ -447,7 +474,7 @@ int blkp_backward(qoc_ctx* c, int order, double* d_dJdu, const int* stale);  // 
 int blku_forward(qoc_ctx* c);
 int blku_backward(qoc_ctx* c, int order, double* d_dJdu);
 int blku_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu);
-int blku_states(qoc_ctx* c);    // rebuild x_k after a segmented eval (no-op unless X_lazy)
+int blku_states(qoc_ctx* c);    // rebuild x_k after a segmented eval (no-op unless fwd.lazy)
 int blku_costates(qoc_ctx* c);  // qoc_get_costates after the fused block backward
 
 // ---- qoc_run_blkseg.hip ----

@@ -309,7 +309,7 @@ template <typename S, typename... A>
 static hipError_t blk_launch(const qoc_ctx* c, S sel, int blocks, int thr, size_t lds, const A&... a) {
   using std::integral_constant;
   auto go = [&](auto K_) {
-    auto kern = c->cheb_ran ? sel(K_, std::true_type()) : sel(K_, std::false_type());
+    auto kern = c->fwd.steps_cheb ? sel(K_, std::true_type()) : sel(K_, std::false_type());
     const hipError_t q = decltype(K_)::value < 100 ? blk_lds_attr(kern, lds) : hipSuccess;
     if (q != hipSuccess) return q;
     hipLaunchKernelGGL(kern, dim3(blocks), dim3(thr), lds, c->stream, a...);
@@ -338,7 +338,6 @@ int blk_forward(qoc_ctx* c) {
   const hipError_t e = blk_launch(c, BLK_KERNELS(k_blkrot_fwd, k_blk_fwd), c->B, blk_threads(c), blk_lds_of(c), g, bk);
   mark_end(c, mk);
   if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "k_blk_fwd launch: %s", hipGetErrorString(e));
-  c->fwd_captured = false;
   c->props_since_reset++;
   return QOC_OK;
 }
@@ -371,7 +370,7 @@ static int blk_grad(qoc_ctx* c, int order, bool mu_mode, double* d_dJdu) {
 // block gradient for orders 1..4; the exact (Fréchet) gradient runs its own dense kernel on the same λ.
 int blk_backward(qoc_ctx* c, int order, double* d_dJdu) {
   if (blku_on(c)) return blku_backward(c, order, d_dJdu);
-  if (c->steps_stale) {  // the last forward was the stored-propagator eval (blkp): this u's step records first
+  if (c->fwd.steps_old) {  // the last forward was the stored-propagator eval (blkp): this u's step records first
     if (int r0 = tchain_prep(c)) return r0;
   }
   const TChainArgs g = tchain_args(c);
@@ -437,8 +436,7 @@ int blk_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu) {
                                   blk_lds_of(c, bk.nwb), gf, gb, bk);
   mark_end(c, mk);
   if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "k_blk_dual launch: %s", hipGetErrorString(e));
-  c->fwd_captured = false;  // the block backward recomputes its own products
-  c->props_since_reset++;
+  c->props_since_reset++;  // (no captures left for a later backward: the block backward recomputes its own products)
   if (blk_big(c)) {
     const int mg = mark_begin(c, 3);
     r = grad_rr_cap(c, d_dJdu, c->stream, 0, c->Nt, true);
@@ -449,15 +447,15 @@ int blk_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu) {
   if (r) return r;
   HIPCHK(c, hipMemcpyAsync(c->d_coef_mu, c->d_coef, (size_t)c->B * 2 * c->m * sizeof(cx<double>),
                            hipMemcpyDeviceToDevice, c->stream));
-  c->L_is_mu = true;
-  c->last_eval_mode = 4;
+  c->bwd.is_mu = true;
+  c->bwd.route = 4;
   return QOC_OK;
 }
 
 int blk_materialize(qoc_ctx* c) {
   int r = QOC_OK;
-  if (c->X_lazy) r = blku_states(c);
-  if (r == QOC_OK && c->L_lazy) r = blku_costates(c);
+  if (c->fwd.lazy) r = blku_states(c);
+  if (r == QOC_OK && c->bwd.lazy) r = blku_costates(c);
   return r;
 }
 

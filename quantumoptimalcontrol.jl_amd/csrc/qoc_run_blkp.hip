@@ -49,11 +49,11 @@ static int blkp_zero_dead(qoc_ctx* c, const BlkArgs& bk, bool lam) {
   return lam ? blk_zero_dead(c, {c->d_X, c->d_L}) : blk_zero_dead(c, {c->d_X});
 }
 // a forward from propagators formed without step records: d_steps still holds the last k_tchain_prep's records, not
-// this u's (the Chebyshev backward re-preps first)
-static void blkp_forward_done(qoc_ctx* c) {
-  c->fwd_captured = false;
+// this u's (the Chebyshev backward re-preps first); ichain: the chains that ran (blkp_ichain_on), for qoc_get_info
+static void blkp_forward_done(qoc_ctx* c, int ichain) {
   c->props_since_reset++;
-  c->steps_stale = true;
+  c->fwd.steps_old = true;
+  c->fwd.formed_ichain = ichain;
 }
 
 // the propagator store d_blkU of at least `bytes` (reallocated when a larger batch part or block layout needs more);
@@ -577,7 +577,7 @@ static int blkp_plan(qoc_ctx* c, const BlkArgs& bk, int parts, BlkpPlan& pl, boo
     const int ri = blkp_interp_setup(c, bk, pl.ia);
     if (ri > 1 || ri < 0) return ri;
     pl.interp = ri == 0;
-    c->last_int_D = pl.interp ? pl.ia.D : 0;
+    c->fwd.formed_D = pl.interp ? pl.ia.D : 0;
   }
   return QOC_OK;
 }
@@ -841,16 +841,16 @@ int blkp_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu, const BlkArgs& b
   BlkpPlan pl;
   if ((r = blkp_plan(c, bk, parts, pl))) return r;
   if (exact && !pl.interp) return 1;  // no curve to differentiate: the caller's dense path, nothing launched here
-  c->ichain_last = blkp_ichain_on(c, bk, pl);
-  if (c->ichain_last) {  // both chains interpolate their own propagators: nothing stored
+  const int ichain = blkp_ichain_on(c, bk, pl);
+  if (ichain) {  // both chains interpolate their own propagators: nothing stored
     if ((r = blkp_zero_dead(c, bk, true))) return r;
     if ((r = blkp_launch_ichain(c, gf, gb, bk, pl.ia, true, 0, nullptr))) return r;
-    blkp_forward_done(c);
+    blkp_forward_done(c, ichain);
     if ((r = exact ? blkp_launch_grad_exact(c, bk, d_dJdu, nullptr, c->d_coef_mu)
                    : blkp_launch_grad(c, bk, d_dJdu, nullptr, c->d_coef_mu)))
       return r;
-    c->L_is_mu = true;
-    c->last_eval_mode = 7;
+    c->bwd.is_mu = true;
+    c->bwd.route = 7;
     return QOC_OK;
   }
   if ((r = blkp_ensure_store(c, nslab * slab * sizeof(double2), true))) return r;  // 1: does not fit
@@ -891,12 +891,12 @@ int blkp_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu, const BlkArgs& b
     HIPCHK(c, hipEventRecord(c->sync_ev[2 * parts], c->stream2));
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->sync_ev[2 * parts], 0));
   }
-  blkp_forward_done(c);
+  blkp_forward_done(c, 0);
   if ((r = exact ? blkp_launch_grad_exact(c, bk, d_dJdu, nullptr, c->d_coef_mu)
                  : blkp_launch_grad(c, bk, d_dJdu, nullptr, c->d_coef_mu)))
     return r;
-  c->L_is_mu = true;
-  c->last_eval_mode = 7;
+  c->bwd.is_mu = true;
+  c->bwd.route = 7;
   return QOC_OK;
 }
 
@@ -931,16 +931,20 @@ int blkp_forward(qoc_ctx* c) {
   BlkpPlan pl;
   if ((r = blkp_plan(c, bk, parts, pl))) return r;
   const TChainArgs gf = tchain_args(c);
-  c->ichain_last = blkp_ichain_on(c, bk, pl);
-  c->ichain_fwd = c->ichain_last != 0;
-  c->blkp_fwd_nwb = bk.nwb;
-  c->blkp_fwd_interp = pl.interp;
-  if (c->ichain_fwd) {  // the forward chain interpolates its propagators; grape_sensitivity's μ recurrence will too
+  const int ichain = blkp_ichain_on(c, bk, pl);
+  // what either end leaves for grape_sensitivity (blkp_backward_ok, blkp_backward)
+  auto done = [&]() {
+    blkp_forward_done(c, ichain);
+    c->fwd.kind = 2;
+    c->fwd.ichain = ichain != 0;
+    c->fwd.nwb = bk.nwb;
+    c->fwd.interp = pl.interp;
+    return QOC_OK;
+  };
+  if (ichain) {  // the forward chain interpolates its propagators; grape_sensitivity's μ recurrence will too
     if ((r = blkp_zero_dead(c, bk, false))) return r;
     if ((r = blkp_launch_ichain(c, gf, gf, bk, pl.ia, false, 0, nullptr, pen))) return r;
-    blkp_forward_done(c);
-    c->fwd_kind = 2;
-    return QOC_OK;
+    return done();
   }
   if ((r = blkp_ensure_store(c, (size_t)c->B * per_seed * 256 * sizeof(double2), true))) return r;
   if ((r = blkp_zero_dead(c, bk, false))) return r;
@@ -965,16 +969,14 @@ int blkp_forward(qoc_ctx* c) {
     HIPCHK(c, hipEventRecord(c->sync_ev[parts], c->stream2));
     HIPCHK(c, hipStreamWaitEvent(c->stream, c->sync_ev[parts], 0));
   }
-  blkp_forward_done(c);
-  c->fwd_kind = 2;
-  return QOC_OK;
+  return done();
 }
 
 bool blkp_backward_ok(const qoc_ctx* c, int order) {
   // the exact gradient: the derivative of the curve the propagate interpolated on (blkp_exact_on)
-  const bool ord_ok = order == 3 || (order == QOC_DUKDP_EXACT && blkp_exact_on(c) && c->blkp_fwd_interp);
-  if (!(c->fwd_kind == 2 && ord_ok && (c->cost_kind == QOC_COST_TRACE || c->cost_kind == QOC_COST_ZCAL) &&
-        (c->ichain_fwd || c->d_blkU)))
+  const bool ord_ok = order == 3 || (order == QOC_DUKDP_EXACT && blkp_exact_on(c) && c->fwd.interp);
+  if (!(c->fwd.kind == 2 && ord_ok && (c->cost_kind == QOC_COST_TRACE || c->cost_kind == QOC_COST_ZCAL) &&
+        (c->fwd.ichain || c->d_blkU)))
     return false;
   const int pmode = blkp_pen_mode(c);
   if (pmode == 2) return false;                                                   // the Chebyshev block chains
@@ -1000,16 +1002,16 @@ int blkp_backward(qoc_ctx* c, int order, double* d_dJdu, const int* stale) {
   const BlkpPen* const pen = lam ? &pp : nullptr;
   TChainArgs gb = tchain_args(c);
   gb.mu_mode = lam ? 0 : 1;
-  if (bk.nwb != c->blkp_fwd_nwb) {  // the propagators of this layout
+  if (bk.nwb != c->fwd.nwb) {  // the propagators of this layout
     BlkpPlan pl;
     if ((r = blkp_plan(c, bk, 1, pl))) return r;  // (with this layout's N_i when it interpolates)
     if (exact && !pl.interp) return 1;            // this layout's series did not converge: nothing launched
     const long long units = (long long)c->B * c->Nt * bk.nwb;
     if ((r = blkp_ensure_store(c, (size_t)units * 256 * sizeof(double2), false))) return r;
     if ((r = blkp_launch_exp(c, pl, 0, units, (double2*)c->d_blkU, 0))) return r;
-    c->ichain_fwd = false;
-    c->ichain_last = 0;
-    c->blkp_fwd_nwb = bk.nwb;
+    c->fwd.ichain = false;  // the forward's leftovers are now the stored propagators of this layout
+    c->fwd.formed_ichain = 0;
+    c->fwd.nwb = bk.nwb;
   }
   // the dead rows of d_L (a no-op unless a sourced backward, or co-states from before x0 or the target moved to another
   // block, left λ there).  k_zero_rows reads no stale flag, and a refused call must leave the last grape_sensitivity's
@@ -1017,7 +1019,7 @@ int blkp_backward(qoc_ctx* c, int order, double* d_dJdu, const int* stale) {
   if (stale && bk.nwb != c->nwb && blk_dead_pending(c, c->d_L))
     if (const int w = wait_stale_check(c)) return w;
   if ((r = blkp_zero_dead(c, bk, true))) return r;
-  if (c->ichain_fwd) {  // the propagate interpolated: the μ recurrence from the same coefficients (the same u)
+  if (c->fwd.ichain) {  // the propagate interpolated: the μ recurrence from the same coefficients (the same u)
     BlkpIntArgs ia;
     blkp_interp_args(c, bk, ia);
     if ((r = blkp_launch_ichain(c, gb, gb, bk, ia, false, 1, stale, pen))) return r;
@@ -1031,8 +1033,9 @@ int blkp_backward(qoc_ctx* c, int order, double* d_dJdu, const int* stale) {
                  : blkp_launch_grad(c, bk, d_dJdu, stale, lam ? nullptr : c->d_coef_mu, lam)))
     return r;
   if (c->src_on) c->dead_dirty = true;  // λ_k is nonzero on the rows of blocks that carry no state
-  c->L_is_mu = !lam;
-  c->last_eval_mode = 7;
+  c->bwd = {};  // (backward() resets after the split paths: they state the whole record)
+  c->bwd.is_mu = !lam;
+  c->bwd.route = 7;
   return QOC_OK;
 }
 

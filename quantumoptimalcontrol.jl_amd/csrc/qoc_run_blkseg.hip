@@ -145,7 +145,7 @@ static int blkseg_params(qoc_ctx* c, const BlksegShape& s, BlksegParams& sp) {
   const bool direct = c->world == 1 && c->best_out;
   sp.best_res = direct ? c->d_best + 2 + 2 * c->world : nullptr;
   sp.best_out = direct ? c->best_out : nullptr;
-  c->best_direct = direct;
+  c->jbest.direct = direct;
   return QOC_OK;
 }
 
@@ -203,7 +203,7 @@ int blkseg_eval(qoc_ctx* c, int order, const double* d_u, double* d_J, double* d
     // same, and each half is within its registers.  The eval leaves no split forward behind.
     int r = blkseg_forward(c, d_u, d_J);
     if (r) return r;
-    c->fwd_kind = 0;
+    c->fwd.kind = 0;
     c->props_since_reset--;  // (counted by the caller)
     return blkseg_backward(c, order, d_dJdu, nullptr);
   }
@@ -222,12 +222,10 @@ int blkseg_eval(qoc_ctx* c, int order, const double* d_u, double* d_J, double* d
   const hipError_t e = blkseg_launch<BLKSEG_FUSED>(c, order, s, sp);
   mark_end(c, mk);
   if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "k_blkseg_eval launch: %s", hipGetErrorString(e));
-  c->fwd_captured = false;
-  c->L_is_mu = false;
-  c->X_lazy = true;
-  c->L_lazy = true;
-  c->best_ready = true;
-  c->last_eval_mode = 6;
+  c->fwd.lazy = true;
+  c->bwd.lazy = true;
+  c->bwd.route = 6;
+  c->jbest.ready = true;
   return QOC_OK;
 }
 
@@ -268,10 +266,9 @@ int blkseg_forward(qoc_ctx* c, const double* d_u, double* d_J) {
   const hipError_t e = blkseg_launch<BLKSEG_FWD>(c, 1, s, sp);
   mark_end(c, mk);
   if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "k_blkseg_eval (forward) launch: %s", hipGetErrorString(e));
-  c->fwd_captured = false;
-  c->X_lazy = true;
-  c->best_ready = true;
-  c->fwd_kind = 1;
+  c->fwd.lazy = true;
+  c->fwd.kind = 1;
+  c->jbest.ready = true;
   c->props_since_reset++;
   return QOC_OK;
 }
@@ -295,9 +292,9 @@ int blkseg_backward(qoc_ctx* c, int order, double* d_dJdu, const int* stale) {
   const hipError_t e = blkseg_launch<BLKSEG_BWD>(c, order, s, sp);
   mark_end(c, mk);
   if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "k_blkseg_eval (backward) launch: %s", hipGetErrorString(e));
-  c->L_is_mu = false;
-  c->L_lazy = true;
-  c->last_eval_mode = 6;
+  c->bwd = {};  // (backward() resets after the split paths: they state the whole record)
+  c->bwd.lazy = true;
+  c->bwd.route = 6;
   return QOC_OK;
 }
 

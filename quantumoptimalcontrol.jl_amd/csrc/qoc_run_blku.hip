@@ -164,7 +164,6 @@ int blku_forward(qoc_ctx* c) {
   const hipError_t e = blku_launch_fwd(c, s, bp);
   mark_end(c, mk);
   if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "k_blku_fwd launch: %s", hipGetErrorString(e));
-  c->fwd_captured = false;
   c->props_since_reset++;
   return QOC_OK;
 }
@@ -258,8 +257,8 @@ static int blku_bwdg(qoc_ctx* c, int order, double* d_dJdu, const double2* Uin =
   }
   HIPCHK(c, hipMemcpyAsync(c->d_u_lam, c->d_u, nu_t * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_coef_lam, c->d_coef, ncf * sizeof(cx<double>), hipMemcpyDeviceToDevice, c->stream));
-  c->L_lazy = true;
-  c->last_eval_mode = 5;
+  c->bwd.lazy = true;
+  c->bwd.route = 5;
   return QOC_OK;
 }
 
@@ -287,9 +286,9 @@ static int blku_states_of(qoc_ctx* c, const double* d_u) {
 // x_k of the last segmented eval: the block forward chain on the u it left in d_u (the eval's own J and coefficients
 // stay as they were)
 int blku_states(qoc_ctx* c) {
-  if (!c->X_lazy) return QOC_OK;
+  if (!c->fwd.lazy) return QOC_OK;
   const int r = blku_states_of(c, c->d_u);
-  if (r == QOC_OK) c->X_lazy = false;
+  if (r == QOC_OK) c->fwd.lazy = false;
   return r;
 }
 
@@ -298,7 +297,7 @@ int blku_states(qoc_ctx* c) {
 // first (into d_X, which then counts as lazy again: the last propagate's u may be another).  qoc_set_state_penalty
 // materialises before it changes the penalty, so the one in force here is the eval's.
 int blku_costates(qoc_ctx* c) {
-  if (!c->L_lazy) return QOC_OK;
+  if (!c->bwd.lazy) return QOC_OK;
   TChainArgs g = tchain_args(c);
   g.coef = c->d_coef_lam;
   g.u = c->d_u_lam;
@@ -306,7 +305,7 @@ int blku_costates(qoc_ctx* c) {
   int r = QOC_OK;
   if (g.pmask) {
     if ((r = blku_states_of(c, c->d_u_lam))) return r;
-    c->X_lazy = true;
+    c->fwd.lazy = true;
   }
   const BlkuShape s = blku_shape(c, false);
   BlkuParams bp = blku_params(c, s);
@@ -314,7 +313,7 @@ int blku_costates(qoc_ctx* c) {
   if (r) return r;
   const hipError_t e = blku_launch_bwd(c, g, s, bp, g.pmask != nullptr);
   if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "k_blku_bwd launch: %s", hipGetErrorString(e));
-  c->L_lazy = false;
+  c->bwd.lazy = false;
   return QOC_OK;
 }
 
@@ -369,7 +368,6 @@ int blku_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu) {
   const hipError_t e = blku_launch_fwd(c, s, bp);
   mark_end(c, mk);
   if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "k_blku_fwd launch: %s", hipGetErrorString(e));
-  c->fwd_captured = false;
   c->props_since_reset++;
   if (fused) {
     r = blku_bwdg(c, order, d_dJdu, storeu ? (const double2*)c->d_blkU : nullptr);
@@ -379,10 +377,9 @@ int blku_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu) {
     mark_end(c, mb);
     if (eb != hipSuccess) return fail(c, QOC_ERR_HIP, "k_blku_bwd launch: %s", hipGetErrorString(eb));
     r = blku_grad(c, order, false, d_dJdu);
-    c->last_eval_mode = 4;  // the block chains' eval, λ in HBM
   }
   if (r) return r;
-  c->L_is_mu = false;
+  if (!fused) c->bwd.route = 4;  // the block chains' eval, λ in HBM
   return QOC_OK;
 }
 

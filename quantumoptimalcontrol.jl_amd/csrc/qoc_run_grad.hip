@@ -112,7 +112,7 @@ int grad_cap_launch(qoc_ctx* c, double* d_dJdu, hipStream_t st, int k0, int nk, 
     a.mur[j] = j <= c->nu ? c->tprm.mur[j] : 0.0;
     a.mui[j] = j <= c->nu ? c->tprm.mui[j] : 0.0;
   }
-  a.kappa = c->cheb_ran ? 2.0 : 1.0;
+  a.kappa = c->fwd.steps_cheb ? 2.0 : 1.0;
   a.coef = mu_mode ? c->d_coef : nullptr;
   a.rsec_mask = 0;
   if (c->packed)

@@ -149,8 +149,8 @@ int tchain_prep(qoc_ctx* c) {
                        c->d_steps, c->d_terms);
   mark_end(c, mk);
   HIPCHK(c, hipGetLastError());
-  c->cheb_ran = cheb;
-  c->steps_stale = false;
+  c->fwd.steps_cheb = cheb;
+  c->fwd.steps_old = false;  // (a backward's re-prep after a forward on propagators formed without them)
   return QOC_OK;
 }
 
@@ -166,15 +166,14 @@ int tchain_forward(qoc_ctx* c) {
 // the forward chain over the step records tchain_prep wrote (with its captures when the shape takes them)
 template <typename T>
 int tchain_forward_chain(qoc_ctx* c) {
-  const bool cheb = c->cheb_ran;
+  const bool cheb = c->fwd.steps_cheb;
   int mk;
   TChainArgs g = tchain_args(c);
-  c->fwd_captured = false;
-  if (tchain_cap_ok(c) && ensure_pws(c) == QOC_OK) {  // P1 / P2 of the gradient as by-products
+  const bool cap = tchain_cap_ok(c) && ensure_pws(c) == QOC_OK;  // P1 / P2 of the gradient as by-products
+  if (cap) {
     const size_t bufN = (size_t)c->N * ((size_t)c->B * (c->Nt + 1) * c->m);
     g.cap1 = c->d_pws;
     g.cap2 = (cx<double>*)c->d_pws + bufN;
-    c->fwd_captured = true;
   }
   if (tchain_mf(c)) {
     const size_t lds = tchain_mf_lds(c->N, c->m, c->nu, tchain_mf_rot(c));
@@ -190,6 +189,7 @@ int tchain_forward_chain(qoc_ctx* c) {
     });
     mark_end(c, mk);
     if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "k_tchain_mf_fwd launch: %s", hipGetErrorString(e));
+    c->fwd.captured = cap;
     c->props_since_reset++;
     return QOC_OK;
   }
@@ -206,6 +206,7 @@ int tchain_forward_chain(qoc_ctx* c) {
   });
   mark_end(c, mk);
   if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "k_tchain_fwd launch: %s", hipGetErrorString(e));
+  c->fwd.captured = cap;
   c->props_since_reset++;
   return QOC_OK;
 }
@@ -232,7 +233,7 @@ int tchain_backward(qoc_ctx* c, int k_lo, int k_hi, hipStream_t st, int flags) {
     hipError_t e = tchain_mf_dispatch(c, [&](auto KQ_) {
       constexpr int KQ = decltype(KQ_)::value;
       // the (P, s, coefficients) of the forward pass are reused: the same polynomial as the states'
-      auto kern = mf_bwd_kernel<KQ>(tchain_mf_maxt(c->N, c->m, c->nu), c->cheb_ran);
+      auto kern = mf_bwd_kernel<KQ>(tchain_mf_maxt(c->N, c->m, c->nu), c->fwd.steps_cheb);
       hipError_t r = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (r != hipSuccess) return r;
       hipLaunchKernelGGL(kern, dim3(c->B), dim3(threads), lds, st, g);
@@ -425,7 +426,7 @@ int tchain_backward_captured(qoc_ctx* c, double* d_dJdu) {
     mark_end(c, mk, c->stream2);
     if (r) return join(r);
   }
-  c->last_eval_mode = 1;
+  c->bwd.route = 1;
   return join(QOC_OK);
 }
 
@@ -456,7 +457,7 @@ int tchain_eval_concurrent(qoc_ctx* c, double* d_dJdu) {
     // μ recurrence beside the forward chain: two launches on two streams
     r = tchain_backward<T>(c, 0, c->Nt, c->stream2, TB_CAPTURE | TB_MU);
     if (r == QOC_OK) r = tchain_forward_chain<T>(c);
-    if (r == QOC_OK && !c->fwd_captured) r = fail(c, QOC_ERR_STATE, "concurrent eval: forward captures missing");
+    if (r == QOC_OK && !c->fwd.captured) r = fail(c, QOC_ERR_STATE, "concurrent eval: forward captures missing");
     const hipError_t e1 = hipEventRecord(c->sync_ev[1], c->stream2);
     const hipError_t e2 = e1 == hipSuccess ? hipStreamWaitEvent(c->stream, c->sync_ev[1], 0) : e1;
     if (r) return r;
@@ -475,7 +476,7 @@ int tchain_eval_concurrent(qoc_ctx* c, double* d_dJdu) {
     const int mk = mark_begin(c, 1);
     hipError_t e = tchain_mf_dispatch(c, [&](auto KQ_) {
       constexpr int KQ = decltype(KQ_)::value;
-      auto kern = c->cheb_ran ? k_tchain_mf_dual<KQ, true, 256> : k_tchain_mf_dual<KQ, false, 256>;
+      auto kern = c->fwd.steps_cheb ? k_tchain_mf_dual<KQ, true, 256> : k_tchain_mf_dual<KQ, false, 256>;
       hipError_t q = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (q != hipSuccess) return q;
       hipLaunchKernelGGL(kern, dim3(2 * c->B), dim3(threads), lds, c->stream, gf, gb);
@@ -483,7 +484,7 @@ int tchain_eval_concurrent(qoc_ctx* c, double* d_dJdu) {
     });
     mark_end(c, mk);
     if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "k_tchain_mf_dual launch: %s", hipGetErrorString(e));
-    c->fwd_captured = true;
+    c->fwd.captured = true;
     c->props_since_reset++;
   }
   const int mk = mark_begin(c, 3);
@@ -493,8 +494,8 @@ int tchain_eval_concurrent(qoc_ctx* c, double* d_dJdu) {
   // the coefficients that turn μ into λ, kept for qoc_get_costates (a later forward rewrites d_coef)
   HIPCHK(c, hipMemcpyAsync(c->d_coef_mu, c->d_coef, (size_t)c->B * 2 * c->m * sizeof(cx<double>),
                            hipMemcpyDeviceToDevice, c->stream));
-  c->L_is_mu = true;
-  c->last_eval_mode = c->concurrent == 2 ? 2 : 3;
+  c->bwd.is_mu = true;
+  c->bwd.route = c->concurrent == 2 ? 2 : 3;
   return QOC_OK;
 }
 

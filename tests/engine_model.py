@@ -1,13 +1,23 @@
 """A stateless model of one live engine context, the op sequences drawn against it and the runner that applies a
 sequence to a GrapeEngine and to the model side by side (tests/test_gpu_call_sequences.py).
 
-The model holds the current settings (names into a System's tables) and two snapshots, nothing else:
+The model holds the current settings (names into a System's tables) and three snapshots, nothing else.  The engine
+keeps one record of qoc_ctx per snapshot (csrc/qoc_internal.hpp), named beside each:
 
     fwd   the controls (or spline coefficients), the settings and the call form of the last successful propagate /
-          eval; None after anything that clears the engine's have_prop
+          eval; None after anything that clears the engine's fwd.valid.
+          LastFwd fwd: valid; kind (what a propagate left for the split sensitivity), lazy (x_k rebuilt on demand),
+          captured, ichain / nwb / interp (the block-propagator forward's leftovers), steps_old / steps_cheb (the step
+          records), formed_D / formed_ichain (report only); the host copies h_u, h_coef for the stale check (coef_ok)
     bwd   the forward it ran on, the settings at that time, the order and lambda_final of the last successful
-          sensitivity / eval
-    jfwd  the forward whose J the engine's J buffer still holds (setters do not clear it): allgather_best
+          sensitivity / eval.
+          LastBwd bwd: is_mu (d_L holds mu_k), lazy (lambda_k rebuilt on demand), route (info()["backward"])
+    jfwd  the forward whose J the engine's J buffer still holds (setters do not clear it): allgather_best.
+          LastJ jbest: ready (the eval already found the best pair), direct (and wrote it out)
+
+"set" below is the record assigned plain (c->fwd = {}, c->bwd = {}) and then filled by the path that ran; "cleared" is
+fwd.valid = false; "kept" may still be a targeted downgrade that leaves the values the same (set_state_penalty turns
+fwd.kind 1 into 0: the sensitivity rebuilds x_k).
 
 Every value is the oracle's (oracle/qoc_oracle.py) from scratch on a snapshot, memoised on the names.  The contract,
 from include/qoc.h and, where the header is silent, csrc/qoc_engine.hip.  A NEW CACHED QUANTITY OF THE ENGINE BELONGS IN
@@ -50,11 +60,16 @@ After a predicted error the model is unchanged and the context behaves as if the
 import functools
 import os
 import pprint
+import sys
 from collections import namedtuple
 
 import numpy as np
 
-import qoc_oracle as O
+if __name__ == "__main__":  # run as a script (pinned_routes): the import paths tests/conftest.py sets under pytest
+    _root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path[:0] = [os.path.join(_root, "quantumoptimalcontrol.jl_amd"), os.path.join(_root, "oracle")]
+
+import qoc_oracle as O  # noqa: E402
 
 B = 3
 ORDERS = (1, 3, 4, "exact")
@@ -594,8 +609,10 @@ class Runner:
         self.s = system(sysname)
         self.m = Model(sysname)
         self.e = make_engine(sysname, monkeypatch)
+        self.e.set_profiling(True)
         self.lastJ = None
         self.infos = {}
+        self.trace = []
         self.ncmp = 0
 
     # -- the engine side of one op ---------------------------------------------------------------------------------
@@ -733,6 +750,14 @@ class Runner:
             assert np.linalg.norm(r) <= 1e-10 * np.linalg.norm(gr[b]), (tag, b, "zcal residual", np.linalg.norm(r) / np.linalg.norm(gr[b]))
             assert abs(t) <= p.dtheta_bound(b), (tag, b, "dtheta", t)
 
+    def _route(self, op):
+        """One row of the route trace: the op's name, what qoc_get_info reports of the records the op left (fwd: split
+        kind, captures, the formation's degree and chain; bwd: the route) and the launches per phase since the last op."""
+        info = self.e.info()
+        n = self.e.phase_times(reset=True)
+        return [op[0], info["backward"], info["split_forward"], int(info["fwd_captured"]), info["interp_degree"],
+                info["interp_chain"]] + [n[k][1] for k in self.e.PHASES]
+
     def run(self):
         try:
             for i, op in enumerate(self.ops):
@@ -742,6 +767,7 @@ class Runner:
                     raise AssertionError(
                         f"{self.sysname} {self.tag}: op {i} {op!r}: {type(ex).__name__}: {ex}\nthe sequence so far, as PINNED "
                         f"takes it:\n{pprint.pformat(self.ops[:i + 1], width=110)}") from ex
+                self.trace.append(self._route(op))
                 self.ncmp += 1
         finally:
             self.e.close()
@@ -842,3 +868,39 @@ PINNED = {
         ("eval", "narrow", 3), ("set_x0", "x0_odd"), ("set_cost", "trace_odd"), ("prop", "narrow"), ("costate", 7, 1),
         ("sens", "narrow", 3), ("costate_dead0", 7, 1)]),
 }
+
+
+# ----------------------------------------------------------------------------------------------------------------------
+# The pinned sequences' route trace
+# ----------------------------------------------------------------------------------------------------------------------
+ROUTES = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "call_sequence_routes.json")
+
+
+def pinned_routes():
+    """tests/golden/call_sequence_routes.json: per PINNED sequence, per op, Runner._route's row.  A pull request that
+    changes a route on purpose regenerates the file on an MI355X, from the repository's root after a build:
+
+        python tests/engine_model.py
+
+    and shows the rows that moved in its diff."""
+    import json
+    with open(ROUTES) as f:
+        return json.load(f)
+
+
+class _Environ:
+    """monkeypatch's two calls, for a run outside pytest."""
+    delenv = staticmethod(os.environ.__delitem__)
+    setenv = staticmethod(os.environ.__setitem__)
+
+
+if __name__ == "__main__":
+    import json
+    import torch
+    torch.empty(1, device="cuda")  # torch's HIP runtime first, as tests/conftest.py built_lib
+    out = sys.argv[1] if len(sys.argv) > 1 else ROUTES
+    traces = {name: Runner(sysname, ops, _Environ, tag=name).run().trace for name, (sysname, ops) in PINNED.items()}
+    with open(out, "w") as f:
+        f.write("{\n" + ",\n".join(f' "{name}": [\n  ' + ",\n  ".join(json.dumps(row) for row in rows) + "]"
+                                   for name, rows in traces.items()) + "\n}\n")
+    print("wrote", out)

@@ -97,7 +97,7 @@ def test_blkp_norm_range(built_lib, monkeypatch, scale):
 
 def test_blkp_eval_then_host_backward(built_lib, monkeypatch):
     """A device eval (stored propagators, no step records) followed by grape_sensitivity on the same u: the block
-    backward prepares its step records first (steps_stale) and gives the oracle's gradient for every order."""
+    backward prepares its step records first (fwd.steps_old) and gives the oracle's gradient for every order."""
     from qoc_amd import systems
     Nt = 40
     prob = systems.tunable_bus_problem(Nt=Nt, tgate=350.0 * Nt / 2000)

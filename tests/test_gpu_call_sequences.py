@@ -14,6 +14,9 @@ on a GrapeEngine and on the model; after every op the two are compared:
     dead rows      exactly 0.0 where a pinned sequence says so
     allgather_best equal to (J.min(), offset + argmin) of the J the engine returned itself
     errors         the exception class and code; the reference's message for a stale u
+    routes         the pinned sequences only: after every op info()'s backward, split_forward, fwd_captured,
+                   interp_degree and interp_chain and the launches per phase since the op before, equal to the rows of
+                   tests/golden/call_sequence_routes.json (engine_model.pinned_routes says how it is regenerated)
 
 On a mismatch the failure names the system, the seed and the op, and prints the sequence so far as the literal that
 PINNED takes.  The systems, all at B = 3 in fp64 (default environment plus QOC_BLOCKS=1): cavity20 (10 blocks of 2 rows,
@@ -42,6 +45,10 @@ def test_pinned_sequence(built_lib, monkeypatch, name):
     system, ops = M.PINNED[name]
     r = M.Runner(system, ops, monkeypatch, tag=name).run()
     assert r.ncmp == len(ops)
+    want = M.pinned_routes()[name]  # no op on another path, none with a launch more, than when the file was written
+    assert len(r.trace) == len(want)
+    for i, (got, row) in enumerate(zip(r.trace, want)):
+        assert got == row, (name, i, ops[i], "route", got, "recorded", row)
 
 
 def test_sequences_cover_the_transitions():
