@@ -208,6 +208,35 @@ int qoc_set_propagation(qoc_ctx* ctx, int method, int nsub);
 #define QOC_ENV_SINEBASIS 2
 int qoc_propagate_envelope(qoc_ctx* ctx, int kind, const double* params, int np, double tgate, double dt,
                            double* J_out, double* x_out);
+/* J and dJ/dp of qoc_propagate_envelope's run for all B seeds in one call: the discrete adjoint of the fixed-step
+ * Tsit5 scheme, i.e. the derivative of the J the engine computes (not the continuous adjoint re-integrated), so a
+ * line search sees a consistent (f, g) at any dt.  Convention: dJ = Re<lambda, dx> with lambda_N = dJ/dx(x(tgate))
+ * (compute_u_sensitivity, src/gradient_computations.jl:217-223); dJdp_out[b*np + q] = dJ/dp_q of seed b, in the order
+ * of params.  Arguments, checks and errors as qoc_propagate_envelope; J is that call's J bit for bit (no state penalty
+ * on the envelope path).  QOC_COST_TRACE and QOC_COST_ZCAL in both forms; QOC_COST_EXTERNAL in the host form only,
+ * with lambda_final (B x N x m) required and J_out left untouched (the _dev form returns QOC_ERR_ARG there).
+ * QOC_ERR_UNSUPPORTED on a QOC_FP32 context and with qoc_set_compression active.
+ *   d/dp_0 of QOC_ENV_DRAG (tgate) and QOC_ENV_SINEBASIS (Tgate) is the partial derivative of the pulse formula: the
+ *     integration horizon is the argument tgate, held fixed.
+ *   QOC_ENV_TUNABLE_BUS: d/dt_plateau and d/dt_rise_fall take the branch of cos_envelope that t lies in (the envelope
+ *     is C^1 in both).  sqrt|cos(theta)| has no derivative at cos(theta) = 0: J is not differentiable where the pulse
+ *     reaches theta/pi = 1/2 + k at a stage time, and the result there is not guaranteed finite (the reference's
+ *     pulse keeps theta/pi within 0.25 +- 0.13).
+ *   A parameter the pulse does not read (beyond the kind's list, or the last one of an even np in the sine basis) has
+ *     derivative 0.
+ * The reverse sweep needs every x_n: the forward stores checkpoints every C steps in a workspace kept on the context
+ * (grown when a call needs more; C = 1 while B x nsteps x m x N x 32 bytes fit min(1 GiB, free / 4), else the
+ * smallest spacing that fits) and the adjoint re-runs each segment from its checkpoint with the forward's arithmetic,
+ * so dJdp does not depend on C in any bit.  QOC_ERR_UNSUPPORTED when the spacing needed exceeds what the LDS holds
+ * beside the generators.  QOC_ENV_WS_MB=<MiB> (read at the context's first such call) replaces the budget;
+ * QOC_ENV_CKPT=<C> at qoc_create forces the spacing (testing; bounded by the same LDS ring).
+ * The call leaves on the context what qoc_propagate_envelope leaves (x(tgate), J) and nothing else: the co-states of
+ * the last grape_sensitivity / eval stay readable.  The _dev form is queued on qoc_stream: d_params (B x np), d_J (B,
+ * may be NULL) and d_dJdp (B x np) are device pointers, and nothing synchronises once the workspace exists. */
+int qoc_eval_envelope(qoc_ctx* ctx, int kind, const double* params, int np, double tgate, double dt,
+                      const double* lambda_final, double* J_out, double* dJdp_out, double* x_out);
+int qoc_eval_envelope_dev(qoc_ctx* ctx, int kind, const double* d_params, int np, double tgate, double dt,
+                          double* d_J, double* d_dJdp);
 
 /* Engine facts: info[0] = path (0 = LDS-resident kernels, 1 = large-N chunked GEMM pipeline),
  * info[1] = slices per chunk (large-N), info[2] = Newton-Schulz iterations executed so far (large-N),

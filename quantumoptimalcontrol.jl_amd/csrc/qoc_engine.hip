@@ -558,6 +558,7 @@ int qoc_create(qoc_ctx** out, int device, int N, int m, int nu, int Nt, int B, i
   if (env_set("QOC_CONCURRENT")) c->concurrent = std::max(0, std::min(2, env_int("QOC_CONCURRENT", 0)));
   c->tchain_rot = env_int("QOC_TCHAIN_ROT", c->tchain_rot);
   c->exact_series = env_int("QOC_GRAD_EXACT_SERIES", 1) != 0;
+  c->env_ckpt = std::max(0, env_int("QOC_ENV_CKPT", 0));
   hipMemset(c->d_L, 0, (size_t)B * (Nt + 1) * Nm * c->esz);
   *out = c;
   return QOC_OK;
@@ -587,7 +588,7 @@ void qoc_destroy(qoc_ctx* c) {
   if (c->h_flag) hipHostFree(c->h_flag);
   if (c->flag_ev) hipEventDestroy(c->flag_ev);
   void* ptrs[] = {c->d_A, c->d_x0, c->d_Xt, c->d_pmask, c->d_u,    c->d_U,    c->d_X, c->d_L, c->d_u_lam, c->d_coef_lam, c->d_blkU, c->d_J_scr, c->d_coef_scr,
-                  c->d_J, c->d_coef, c->d_dJdu, c->d_flag, c->d_hist, c->d_stage, c->d_ws, c->d_red, c->d_Bs, c->d_cstage, c->d_fws, c->d_AH, c->d_Cst, c->d_gws, c->d_pws, c->d_ps, c->d_At, c->d_steps, c->d_terms, c->d_src, c->d_rsec, c->d_sink, c->d_blkrec, c->d_xn};
+                  c->d_J, c->d_coef, c->d_dJdu, c->d_flag, c->d_hist, c->d_stage, c->d_ws, c->d_red, c->d_Bs, c->d_cstage, c->d_fws, c->d_AH, c->d_Cst, c->d_gws, c->d_pws, c->d_ps, c->d_At, c->d_steps, c->d_terms, c->d_src, c->d_rsec, c->d_sink, c->d_blkrec, c->d_xn, c->d_env_ws, c->d_env_p, c->d_env_lam};
   for (void* p : ptrs)
     if (p) hipFree(p);
   for (auto& m : c->marks) {
@@ -1373,6 +1374,84 @@ int qoc_propagate_envelope(qoc_ctx* c, int kind, const double* params, int np, d
     }
   }
   if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "qoc_propagate_envelope: %s", hipGetErrorString(e));
+  return QOC_OK;
+}
+
+// qoc_eval_envelope / _dev: qoc_propagate_envelope's argument checks, then what the adjoint does not cover
+static int env_eval_check(qoc_ctx* c, int kind, const void* params, int np, double tgate, double dt, const void* dJdp,
+                          long long* nsteps) {
+  int r = check_ready(c);
+  if (r) return r;
+  if (!params || np < 1 || np > 64) return fail(c, QOC_ERR_ARG, "bad parameter array");
+  if (!dJdp) return fail(c, QOC_ERR_ARG, "dJdp is null");
+  if (kind < QOC_ENV_TUNABLE_BUS || kind > QOC_ENV_SINEBASIS) return fail(c, QOC_ERR_ARG, "unknown envelope %d", kind);
+  const int need_nu = kind == QOC_ENV_TUNABLE_BUS ? 1 : 2;
+  if (c->nu != need_nu) return fail(c, QOC_ERR_ARG, "envelope %d drives %d controls, context has nu=%d", kind, need_nu, c->nu);
+  if (c->big || c->N > 64) return fail(c, QOC_ERR_UNSUPPORTED, "the Tsit5 path runs on the LDS-resident sizes (N <= 64)");
+  if (!(dt > 0) || !(tgate > 0)) return fail(c, QOC_ERR_ARG, "tgate and dt must be positive");
+  if (c->prec != QOC_FP64)
+    return fail(c, QOC_ERR_UNSUPPORTED, "qoc_eval_envelope: the envelope gradient is fp64 only (QOC_FP32 context)");
+  if (c->packed)
+    return fail(c, QOC_ERR_UNSUPPORTED, "qoc_eval_envelope: not with qoc_set_compression active (packed states)");
+  const size_t env_lds = (size_t)(c->nu + 1) * c->N * c->N * c->esz;
+  if (env_lds > 160 * 1024) return fail(c, QOC_ERR_UNSUPPORTED, "generators (%zu B) exceed the 160 KiB LDS", env_lds);
+  *nsteps = (long long)std::llround(tgate / dt);
+  return QOC_OK;
+}
+
+// forward with checkpoints, terminal cost, adjoint: queued on the stream.  Leaves what qoc_propagate_envelope leaves
+// (forward_begin, x(tgate) in slot Nt, J in d_J, fwd not valid); d_L and the bwd record are not touched.
+static int env_eval_queue(qoc_ctx* c, int kind, const double* dP, int np, double dt, long long nsteps,
+                          const EnvGradPlan& pl, const void* d_lam, double* d_dJdp) {
+  forward_begin(c);
+  hipError_t e = launch_envelope_ckpt(c, kind, dP, np, dt, nsteps, pl);
+  if (e == hipSuccess && c->cost_kind != QOC_COST_EXTERNAL) e = launch_terminal_cost(c);
+  if (e == hipSuccess) e = launch_envelope_grad(c, kind, dP, np, dt, nsteps, pl, d_lam, d_dJdp);
+  if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "qoc_eval_envelope: %s", hipGetErrorString(e));
+  return QOC_OK;
+}
+
+int qoc_eval_envelope_dev(qoc_ctx* c, int kind, const double* d_params, int np, double tgate, double dt, double* d_J,
+                          double* d_dJdp) {
+  long long nsteps = 0;
+  int r = env_eval_check(c, kind, d_params, np, tgate, dt, d_dJdp, &nsteps);
+  if (r) return r;
+  if (c->cost_kind == QOC_COST_EXTERNAL)
+    return fail(c, QOC_ERR_ARG, "QOC_COST_EXTERNAL needs qoc_eval_envelope (host lambda_final)");
+  EnvGradPlan pl;
+  if ((r = env_grad_plan(c, nsteps, &pl))) return r;
+  if ((r = env_eval_queue(c, kind, d_params, np, dt, nsteps, pl, nullptr, d_dJdp))) return r;
+  if (d_J && d_J != c->d_J)
+    HIPCHK(c, hipMemcpyAsync(d_J, c->d_J, c->B * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  return QOC_OK;
+}
+
+int qoc_eval_envelope(qoc_ctx* c, int kind, const double* params, int np, double tgate, double dt,
+                      const double* lambda_final, double* J_out, double* dJdp_out, double* x_out) {
+  long long nsteps = 0;
+  int r = env_eval_check(c, kind, params, np, tgate, dt, dJdp_out, &nsteps);
+  if (r) return r;
+  const bool ext = c->cost_kind == QOC_COST_EXTERNAL;
+  if (ext && !lambda_final) return fail(c, QOC_ERR_ARG, "lambda_final is required for QOC_COST_EXTERNAL");
+  EnvGradPlan pl;
+  if ((r = env_grad_plan(c, nsteps, &pl))) return r;
+  const size_t Nm = (size_t)c->N * c->m;
+  if (!c->d_env_p) HIPCHK(c, hipMalloc((void**)&c->d_env_p, (size_t)c->B * 128 * sizeof(double)));
+  if (ext && !c->d_env_lam) HIPCHK(c, hipMalloc(&c->d_env_lam, (size_t)c->B * Nm * c->esz));
+  double* dP = c->d_env_p;
+  double* dG = c->d_env_p + (size_t)c->B * 64;
+  HIPCHK(c, hipMemcpyAsync(dP, params, (size_t)c->B * np * sizeof(double), hipMemcpyHostToDevice, c->stream));
+  if (ext && (r = upload_states(c, lambda_final, c->d_env_lam, (size_t)c->B, nullptr))) return r;
+  if ((r = env_eval_queue(c, kind, dP, np, dt, nsteps, pl, ext ? c->d_env_lam : nullptr, dG))) return r;
+  HIPCHK(c, hipMemcpyAsync(dJdp_out, dG, (size_t)c->B * np * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  if (J_out && !ext) HIPCHK(c, hipMemcpyAsync(J_out, c->d_J, c->B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (x_out) {
+    for (int b = 0; b < c->B; ++b) {
+      r = download_states(c, (char*)c->d_X + ((size_t)b * (c->Nt + 1) + c->Nt) * Nm * c->esz, x_out + 2 * Nm * b);
+      if (r) return r;
+    }
+  }
   return QOC_OK;
 }
 

@@ -7,7 +7,7 @@
 //   qoc_run_tchain.hip    the Taylor-action chains (k_tchain_*)
 //   qoc_run_grad.hip      the fused order-3 gradient and the exact series gradient (k_grad_rr_*)
 //   qoc_run_big.hip       the large-N GEMM pipeline, the GEMM-shaped gradient and the Fréchet gradient
-//   qoc_run_ode.hip       the Tsit5 path
+//   qoc_run_ode.hip       the Tsit5 path, the envelope run and its discrete adjoint
 //   qoc_run_blk.hip       the block chains and block gradient (generators with small invariant blocks), their router
 //   qoc_run_blkp.hip      blocks of 5..16 rows on stored / interpolating propagators
 //   qoc_run_blku.hip      blocks of <= 4 rows on block propagators
@@ -42,6 +42,14 @@ using namespace qoc;
 struct BlksegShape {
   int W, S, L, UPW, RB;
   size_t lds;
+};
+
+// qoc_eval_envelope's launch shape (qoc_run_ode.hip env_grad_plan): checkpoint spacing, checkpoints per column,
+// conjugate-transposed generator copies in LDS, column waves, the gradient kernel's dynamic LDS
+struct EnvGradPlan {
+  int C = 1, nseg = 0, W = 1;
+  bool tr = false;
+  size_t lds = 0;
 };
 
 // The last successful forward (propagate / eval).  Plain: x_k of the u in d_u are in d_X and nothing else is kept.
@@ -302,6 +310,16 @@ struct qoc_ctx {
   unsigned long long* d_xn = nullptr;   // [0] max n_k, [1] Σ n_k of the last call, then B x Nt term counts (first use)
   size_t xws_budget = 0;                // workspace budget: min(2 GiB, free / 8) or QOC_GRAD_EXACT_WS_MB (first use)
   long long xs_stats[4] = {0, 0, 0, 0};  // qoc_exact_series_stats: units, Σ n_k, largest n_k, fallbacks over the cap
+  // qoc_eval_envelope (qoc_ode_grad.hpp): the checkpoints (x_n, k1_n) every env C steps, scratch that no later call
+  // reads (grown on demand, not counted in dev_bytes: qoc_get_info reports what qoc_propagate_envelope would leave);
+  // the host form's parameters, gradient and caller's λ_N; QOC_ENV_CKPT at qoc_create forces the spacing (0: chosen per
+  // call); the checkpoint budget min(1 GiB, free / 4) or QOC_ENV_WS_MB, read at first use
+  void* d_env_ws = nullptr;
+  size_t env_ws_bytes = 0;
+  double* d_env_p = nullptr;   // B x 64 parameters | B x 64 gradient
+  void* d_env_lam = nullptr;   // B x N x m
+  int env_ckpt = 0;
+  size_t env_budget = 0;
   // packed states (compress_states, src/utils.jl:96-109): two parity sectors share the kernels' columns, so the
   // chains and the gradient run on m = max(n1, n2) columns instead of the caller's m_user = n1 + n2
   int m_user = 0;                       // columns of the caller's states (qoc_create's m)
@@ -415,6 +433,11 @@ template <typename T>
 int ode_adjoint(qoc_ctx* c);
 hipError_t launch_envelope(qoc_ctx* c, int kind, const double* dP, int np, double dt, long long nsteps);
 hipError_t launch_terminal_cost(qoc_ctx* c);
+int env_grad_plan(qoc_ctx* c, long long nsteps, EnvGradPlan* pl);
+hipError_t launch_envelope_ckpt(qoc_ctx* c, int kind, const double* dP, int np, double dt, long long nsteps,
+                                const EnvGradPlan& pl);
+hipError_t launch_envelope_grad(qoc_ctx* c, int kind, const double* dP, int np, double dt, long long nsteps,
+                                const EnvGradPlan& pl, const void* d_lam, double* d_dJdp);
 
 // ---- qoc_run_tchain.hip ----
 bool tchain_mf(const qoc_ctx* c);

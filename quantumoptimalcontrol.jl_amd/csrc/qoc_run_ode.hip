@@ -1,8 +1,9 @@
-// qoc_run_ode.hip — the fixed-step Tsit5 path (qoc_ode.hpp: k_ode_pwc, k_ode_envelope) and the terminal-cost
-// kernel of the paths without a fused forward epilogue.
+// qoc_run_ode.hip — the fixed-step Tsit5 path (qoc_ode.hpp: k_ode_pwc, k_ode_envelope; qoc_ode_grad.hpp: the
+// envelope run's discrete adjoint) and the terminal-cost kernel of the paths without a fused forward epilogue.
 #include "qoc_bgemm.hpp"
 #include "qoc_internal.hpp"
 #include "qoc_ode.hpp"
+#include "qoc_ode_grad.hpp"
 
 namespace qoc_host {
 
@@ -103,6 +104,81 @@ hipError_t launch_terminal_cost(qoc_ctx* c) {
                        (const cx<float>*)c->d_X, (const cx<float>*)c->d_Xt, c->cost_kind, c->cost_n, 0, c->d_J,
                        c->d_coef, sectors(c));
   return hipGetLastError();
+}
+
+// ---- qoc_eval_envelope: checkpoint spacing, workspace, launches (qoc_ode_grad.hpp) ----
+// The spacing C: 1 (every x_n stored, no segment re-run) while the checkpoints fit the workspace budget, else the
+// smallest spacing that does (QOC_ENV_WS_MB sets the budget, read at the first call); QOC_ENV_CKPT forces it.  Either is bounded by the LDS ring of C x N per column wave
+// beside the generators; a forced spacing beyond that runs at the bound.  The conjugate-transposed generator copies
+// are kept when both sets take at most 64 KiB: a function of N and nu alone, so that the spacing does not decide
+// which mat-vec runs.  The workspace grows when a call needs more and stays with the context.
+int env_grad_plan(qoc_ctx* c, long long nsteps, EnvGradPlan* pl) {
+  const size_t gen = (size_t)(c->nu + 1) * c->N * c->N * sizeof(cx<double>);
+  const int W = std::min(c->m, 4);
+  pl->W = W;
+  pl->tr = 2 * gen <= 64 * 1024;
+  const size_t fixed = (pl->tr ? 2 : 1) * gen + (size_t)W * 64 * sizeof(double);
+  const size_t per_c = (size_t)W * c->N * sizeof(cx<double>);
+  if (fixed + per_c > 160 * 1024)
+    return fail(c, QOC_ERR_UNSUPPORTED, "generators (%zu B) leave no LDS for the adjoint's state ring", gen);
+  const long long c_lds = (long long)((160 * 1024 - fixed) / per_c);
+  const size_t per_ckpt = (size_t)c->B * c->m * 2 * c->N * sizeof(cx<double>);
+  if (!c->env_budget) {
+    size_t freeb = 0, totalb = 0;
+    (void)hipMemGetInfo(&freeb, &totalb);
+    c->env_budget = std::max<size_t>(std::min<size_t>(1ull << 30, freeb / 4), 1);
+    if (env_set("QOC_ENV_WS_MB")) c->env_budget = std::max<size_t>((size_t)(env_dbl("QOC_ENV_WS_MB", 0.0) * 1048576.0), 1);
+  }
+  long long C = 1;
+  if (c->env_ckpt > 0) {
+    C = std::min<long long>(c->env_ckpt, c_lds);
+  } else {
+    const long long fit = std::max<long long>(1, (long long)(c->env_budget / per_ckpt));  // checkpoints that fit
+    C = std::max<long long>(1, (nsteps + fit - 1) / fit);
+    if (C > c_lds)
+      return fail(c, QOC_ERR_UNSUPPORTED,
+                  "%lld steps need a checkpoint spacing of %lld in a workspace of %zu MiB; the LDS ring holds %lld",
+                  nsteps, C, c->env_budget >> 20, c_lds);
+  }
+  pl->C = (int)C;
+  pl->nseg = (int)((nsteps + C - 1) / C);
+  pl->lds = fixed + (size_t)pl->C * per_c;
+  const size_t need = std::max<size_t>(1, (size_t)pl->nseg) * per_ckpt;
+  if (need > c->env_ws_bytes) {
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    if (c->d_env_ws) hipFree(c->d_env_ws);
+    c->d_env_ws = nullptr;
+    c->env_ws_bytes = 0;
+    HIPCHK(c, hipMalloc(&c->d_env_ws, need));
+    c->env_ws_bytes = need;
+  }
+  return QOC_OK;
+}
+
+hipError_t launch_envelope_ckpt(qoc_ctx* c, int kind, const double* dP, int np, double dt, long long nsteps,
+                                const EnvGradPlan& pl) {
+  const size_t lds = (size_t)(c->nu + 1) * c->N * c->N * sizeof(cx<double>);
+  hipError_t e = hipFuncSetAttribute((const void*)k_ode_envelope_ckpt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  if (e != hipSuccess) return e;
+  hipLaunchKernelGGL(k_ode_envelope_ckpt, dim3(c->B), dim3(64 * pl.W), lds, c->stream, c->N, c->m, c->nu, c->Nt, kind,
+                     dP, np, dt, nsteps, pl.C, pl.nseg, (const cx<double>*)c->d_A, (const cx<double>*)c->d_x0,
+                     c->x0_per_seed, (cx<double>*)c->d_X, (cx<double>*)c->d_env_ws);
+  return hipGetLastError();
+}
+
+// d_lam: the caller's λ_N (B x N x m, QOC_COST_EXTERNAL) or nullptr: λ_N from d_coef and the target
+hipError_t launch_envelope_grad(qoc_ctx* c, int kind, const double* dP, int np, double dt, long long nsteps,
+                                const EnvGradPlan& pl, const void* d_lam, double* d_dJdp) {
+  auto go = [&](auto kern) {
+    hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
+    if (e != hipSuccess) return e;
+    hipLaunchKernelGGL(kern, dim3(c->B), dim3(64 * pl.W), pl.lds, c->stream, c->N, c->m, kind, dP, np, dt, nsteps, pl.C,
+                       pl.nseg, (const cx<double>*)c->d_A, (const cx<double>*)c->d_env_ws, (const cx<double>*)c->d_Xt,
+                       (const cx<double>*)c->d_coef, (const cx<double>*)d_lam, d_dJdp);
+    return hipGetLastError();
+  };
+  if (c->nu == 1) return pl.tr ? go(k_ode_envelope_grad<1, true>) : go(k_ode_envelope_grad<1, false>);
+  return pl.tr ? go(k_ode_envelope_grad<2, true>) : go(k_ode_envelope_grad<2, false>);
 }
 
 template int ode_forward<double>(qoc_ctx*);

@@ -132,6 +132,35 @@ function QOC.propagate(A0, A::Vector{<:AbstractMatrix}, u, x0, cache::MI355XCach
     return cache.x
 end
 
+const ENVELOPE_KINDS = Dict(:tunable_bus => Cint(0), :drag => Cint(1), :sinebasis => Cint(2))
+
+"""
+    eval_envelope(A0, A, kind, p, x0, tgate, dt, dJfinal_dx, cache) -> (dJdp, x)
+
+Gradient of a terminal cost with respect to the parameters `p` of a parameterised pulse (src/parameterized_pulses.jl;
+`kind` is `:drag`, `:sinebasis` or `:tunable_bus`) for dx/dt = (A0 + Σ_j c_j(t; p) A_j) x integrated with fixed-step
+Tsit5 on [0, tgate] (wrap_envelope, src/QuantumOptimalControl.jl:43-54): the discrete adjoint of that scheme
+(qoc_eval_envelope), i.e. the derivative of the cost of the `x` returned.  The generators are used as given (not
+Δt-scaled).  The closure `dJfinal_dx` is evaluated here at x(tgate) (one forward run, qoc_propagate_envelope) and
+handed over as λ (dJ = Re<λ, dx>).  ∂/∂p[1] of `:drag` / `:sinebasis` holds the horizon `tgate` fixed.
+"""
+function eval_envelope(A0, A::Vector{<:AbstractMatrix}, kind::Symbol, p::AbstractVector, x0, tgate, dt, dJfinal_dx,
+                       cache::MI355XCache)
+    upload!(cache, A0, A, x0)
+    pv = Vector{Float64}(p)
+    x = Matrix{ComplexF64}(undef, cache.N, cache.m)
+    check(ccall((:qoc_propagate_envelope, libqoc), Cint,
+                (Ptr{Cvoid}, Cint, Ptr{Float64}, Cint, Cdouble, Cdouble, Ptr{Float64}, Ptr{ComplexF64}),
+                cache.ctx, ENVELOPE_KINDS[kind], pv, length(pv), tgate, dt, C_NULL, x), cache.ctx)
+    λf = Matrix{ComplexF64}(dJfinal_dx(x))
+    dJdp = zeros(length(pv))
+    check(ccall((:qoc_eval_envelope, libqoc), Cint,
+                (Ptr{Cvoid}, Cint, Ptr{Float64}, Cint, Cdouble, Cdouble, Ptr{ComplexF64}, Ptr{Float64}, Ptr{Float64},
+                 Ptr{ComplexF64}),
+                cache.ctx, ENVELOPE_KINDS[kind], pv, length(pv), tgate, dt, λf, C_NULL, dJdp, x), cache.ctx)
+    return dJdp, x
+end
+
 # grape_sensitivity (src/gradient_computations.jl:35-77) on the GPU; the closure dJfinal_dx is
 # evaluated here at x[end] and handed over as λ_{Nt+1} (QOC_COST_EXTERNAL).  dUkdp_order = 0 (QOC_DUKDP_EXACT) is the
 # exact Fréchet gradient; with this external cost it runs the dense route (the segmented eval and the interpolating

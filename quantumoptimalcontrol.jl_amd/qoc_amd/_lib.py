@@ -73,6 +73,8 @@ SIGNATURES = {
     "qoc_taylor_histogram_n": (C.c_int, [_vp, C.POINTER(C.c_longlong), C.c_int, C.c_int]),
     "qoc_set_propagation": (C.c_int, [_vp, C.c_int, C.c_int]),
     "qoc_propagate_envelope": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, _dp, _dp]),
+    "qoc_eval_envelope": (C.c_int, [_vp, C.c_int, _dp, C.c_int, C.c_double, C.c_double, _dp, _dp, _dp, _dp]),
+    "qoc_eval_envelope_dev": (C.c_int, [_vp, C.c_int, _vp, C.c_int, C.c_double, C.c_double, _vp, _vp]),
     "qoc_get_info": (C.c_int, [_vp, C.POINTER(C.c_longlong)]),
     "qoc_get_info_n": (C.c_int, [_vp, C.POINTER(C.c_longlong), C.c_int]),
     "qoc_set_chain": (C.c_int, [_vp, C.c_int]),

@@ -206,6 +206,40 @@ class GrapeEngine:
         xs = np.stack([_from_cm(x, self.N, self.m) for x in Xc])
         return (J if self.cost_kind == "trace" else None), xs
 
+    def eval_envelope(self, kind: str, params, tgate: float, dt: float, lambda_final=None):
+        """J and dJ/dp of propagate_envelope's run in one call (qoc_eval_envelope): the discrete adjoint of the
+        fixed-step Tsit5 scheme, the derivative of the J the engine computes.  params (B, np) per seed ->
+        (J (B,) or None with an external cost, dJdp (B, np), x(tgate) (B, N, m)).  lambda_final ((B, N, m) complex,
+        dJ = Re<lambda, dx>) is required with set_cost_external() and ignored otherwise.  fp64 contexts without
+        set_compression; d/dp_0 of 'drag' / 'sinebasis' holds the integration horizon tgate fixed."""
+        P = np.ascontiguousarray(params, dtype=np.float64)
+        if P.ndim == 1:
+            P = P[None]
+        if P.shape[0] != self.B:
+            raise ValueError(f"params must be (B={self.B}, np), got {P.shape}")
+        lam = None
+        if lambda_final is not None:
+            lf = np.asarray(lambda_final, dtype=np.complex128)
+            if lf.ndim == 2:
+                lf = lf[None]
+            if lf.shape != (self.B, self.N, self.m):
+                raise ValueError(f"lambda_final must be (B, N, m) = {(self.B, self.N, self.m)}, got {lf.shape}")
+            lam = np.concatenate([_cm_complex(x) for x in lf]).view(np.float64)
+        J = np.zeros(self.B)
+        g = np.zeros((self.B, P.shape[1]))
+        X = np.zeros(2 * self.B * self.N * self.m)
+        self._chk(self._lib.qoc_eval_envelope(self._h, L.QOC_ENV[kind], _ptr(P), P.shape[1], float(tgate), float(dt),
+                                              _ptr(lam) if lam is not None else None, _ptr(J), _ptr(g), _ptr(X)))
+        Xc = X.view(np.complex128).reshape(self.B, self.N * self.m)
+        xs = np.stack([_from_cm(x, self.N, self.m) for x in Xc])
+        return (None if self.cost_kind == "external" else J), g, xs
+
+    def eval_envelope_device(self, kind: str, d_params: int, np_: int, tgate: float, dt: float, d_J: int, d_dJdp: int):
+        """qoc_eval_envelope_dev: d_params (B x np doubles), d_J (B, 0: none) and d_dJdp (B x np) on the device,
+        queued on the engine's stream (no host synchronisation once the checkpoint workspace exists)."""
+        self._chk(self._lib.qoc_eval_envelope_dev(self._h, L.QOC_ENV[kind], C.c_void_p(d_params), int(np_), float(tgate),
+                                                  float(dt), C.c_void_p(d_J or None), C.c_void_p(d_dJdp)))
+
     # ---- hot path (host arrays) ---------------------------------------------------
     def propagate(self, u) -> np.ndarray:
         """Forward pass for all seeds; returns J (B,) = Jfinal(x_N) + sum_k L(x_k)."""
