@@ -76,6 +76,50 @@ int qoc_synchronize(qoc_ctx* ctx);
 
 /* Δt-prescaled generators A0Δt and A_jΔt (src/utils.jl:86-91), N x N each. */
 int qoc_set_generators(qoc_ctx* ctx, const double* A0, const double* const* Aj);
+/* Robust control: every pulse evaluated over an ensemble of E >= 1 generator sets (sampled detunings, couplings,
+ * drive-amplitude calibrations), J̄_b = Σ_e w_e J(u_b; member e), in one launch of the segmented eval with one
+ * workgroup per (pulse, member) and one reduction launch behind it.  A0s: E x N x N, Ajs[j]: E x N x N (column-major
+ * interleaved, members contiguous), each Δt-prescaled like qoc_set_generators' arguments; weights: E values, NULL =
+ * 1/E each.  E = 0 clears (A0s, Ajs and weights are then ignored; no effect when none is set).
+ * Layout: qoc_set_generators comes first (QOC_ERR_STATE otherwise) and its set, the nominal one, fixes the block
+ *   layout: its invariant blocks must have 2 or 3 rows and it must be exactly skew-Hermitian (QOC_ERR_UNSUPPORTED
+ *   otherwise, e.g. dense generators or the tunable bus).  Every non-zero off-diagonal entry of every member must lie
+ *   inside one of those blocks (QOC_ERR_ARG otherwise); members may lack couplings the nominal set has.  The nominal
+ *   set need not be a member: under an ensemble it is not evaluated.
+ * Members and weights: every generator of every member must pass qoc_set_generators' exact skew-Hermitian test
+ *   (|A + A^H| <= 4 eps max|A|) and be finite, else QOC_ERR_ARG.  Weights must be finite and >= 0 with a positive sum
+ *   (QOC_ERR_ARG otherwise) and are used as given, not normalised.  The setter copies everything; a failed call leaves
+ *   the context (and an earlier ensemble) as it was.
+ * With an ensemble set, qoc_eval_dev returns J̄_b = Σ_e w_e J_{b,e} (the state penalty included) and
+ *   dJ̄/du_b = Σ_e w_e dJ_{b,e}/du, the members added in ascending e as acc = fma(w_e, v_e, acc) from 0 (no atomics:
+ *   the result does not depend on scheduling).  Everything built on qoc_eval_dev follows with no change of its own:
+ *   qoc_eval_spline[_dev], qoc_minimize_spline_dev, and the best (J, seed) of qoc_allgather_best[_dev], which is the
+ *   argmin of J̄.  x0 (shared or per seed), the target and the cost are the context's, the same for every member.
+ * Supported where the one-launch segmented eval applies: invariant blocks of 2 or 3 rows, QOC_FP64, QOC_COST_TRACE
+ *   and QOC_COST_ZCAL, orders 1-4 and QOC_DUKDP_EXACT, and the state penalty on blocks of 2 rows.
+ * QOC_ERR_UNSUPPORTED, leaving the context as it was: an eval that kernel does not take (a co-state source,
+ *   QOC_COST_EXTERNAL gives its usual QOC_ERR_STATE, qoc_set_compression, QOC_BLKSEG=0, QOC_CONCURRENT=0, Tsit5); the
+ *   penalised eval on blocks of 3 rows (its two-launch form keeps G and D per seed in HBM); and, while an ensemble is
+ *   set, qoc_propagate[_dev], qoc_grape_sensitivity[_dev], qoc_propagate_spline, qoc_sensitivity_spline,
+ *   qoc_propagate_envelope and qoc_eval_envelope[_dev]: state and co-state are per member, and the split call form is
+ *   not part of the ensemble eval.
+ * What it leaves: the setter (setting or clearing) materialises lazily kept states / co-states and invalidates the
+ *   last forward (qoc_get_states: QOC_ERR_STATE); an ensemble eval keeps no state either and nothing lazy.  The
+ *   co-states of the last plain backward stay readable (as after a refused call), the context's u holds the B pulses,
+ *   and qoc_get_info keeps reporting the last plain backward's route.
+ * Clearing: qoc_set_generators drops the ensemble (also one that fails after its argument checks).  After clearing, a
+ *   plain eval is bitwise what it was before the ensemble was set.
+ * Workspace (allocated by the setter, counted in info[3], freed on clear and qoc_destroy): the members' tables, and
+ *   per (pulse, member) J, 2m λ_N coefficients and Nt x nu values of dJdu.
+ * qoc_ensemble_size: E, 0 = none.  qoc_get_member_costs: J_{b,e} of the last ensemble eval (B x E, member fastest;
+ *   synchronises; QOC_ERR_STATE without an ensemble or before its first eval): the hook for worst-case objectives.
+ * qoc_member_costs_dev: the same buffer on the device (NULL without an ensemble), valid while this ensemble is set and
+ *   written by every ensemble eval on qoc_stream. */
+int qoc_set_generator_ensemble(qoc_ctx* ctx, int E, const double* A0s, const double* const* Ajs,
+                               const double* weights);
+int qoc_ensemble_size(qoc_ctx* ctx);
+int qoc_get_member_costs(qoc_ctx* ctx, double* Jm);
+double* qoc_member_costs_dev(qoc_ctx* ctx);
 /* x0 (N x m) shared by all seeds (per_seed = 0) or B x N x m (per_seed = 1) — propagate :14. */
 int qoc_set_x0(qoc_ctx* ctx, const double* x0, int per_seed);
 /* Terminal cost: kind QOC_COST_TRACE (X_target N x m, normalisation n),

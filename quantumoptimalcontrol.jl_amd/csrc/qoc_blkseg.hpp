@@ -104,6 +104,11 @@ struct BlksegParams {
   unsigned int prow[3];
   unsigned int pcol;
   double2* dseg;
+  // ensemble launches (the ENS instantiations; 0 / nullptr otherwise): E generator sets per pulse, workgroup v =
+  // pulse * E + member; member e reads the table gtab + e * 3 nblk NB^2 and its nine scalars ens[9 e ..] =
+  // rad[3] | mur[3] | mui[3] in place of the ones above
+  int E;
+  const double* ens;
 };
 enum { BLKSEG_FUSED = 0, BLKSEG_FWD = 1, BLKSEG_BWD = 2 };
 
@@ -903,14 +908,51 @@ __device__ __forceinline__ void seg_pen_step(int pm, double f, double2* dp, int 
     }
 }
 
+// a value every lane of the wave holds alike, moved to scalar registers
+__device__ __forceinline__ double seg_uniform(double x) {
+  const long long b = __double_as_longlong(x);
+  const int lo = __builtin_amdgcn_readfirstlane((int)(b & 0xffffffffll)), hi = __builtin_amdgcn_readfirstlane((int)(b >> 32));
+  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+
 // One workgroup per seed (blockIdx.x), W = blockDim / 64 waves, UPW segments of nblk lanes per wave (lanes past
 // UPW nblk idle).  ORD: the gradient's order 1..4, or 0 for the exact one (the header comment's phase 3).
 // Built-in costs only (TRACE / ZCAL), no co-state source, unpacked states, skew-Hermitian generators
 // (the host's blkseg_ok).  PEN: with the state penalty on the rows P and columns C of sp.prow / sp.pcol (the header
 // comment's penalty section); PEN = false is the unpenalised kernel, instruction for instruction.
-template <int NB, int ORD, int WMAX, int MODE = BLKSEG_FUSED, bool PEN = false>
-__global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, const BlkArgs bk, const BlksegParams sp) {
+// ENS (BLKSEG_FUSED only): one workgroup per (pulse, member of a generator ensemble), blockIdx.x = v = pulse * E +
+// member.  The pulse selects the row of u (and of a per-seed x_0), the member its generator table and nine scalars
+// (uniform loads in the prologue); every output (J, the coefficients, dJdu) is indexed by v and goes to the ensemble's
+// workspace, u_copy is written by member 0's workgroups alone, and the second copies and the best-pair epilogue are
+// off.  Phases 1-3 are the same code; ENS = false is the kernel without any of it.
+template <int NB, int ORD, int WMAX, int MODE = BLKSEG_FUSED, bool PEN = false, bool ENS = false>
+__global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, const BlkArgs bk, const BlksegParams sp_) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  static_assert(!ENS || MODE == BLKSEG_FUSED, "the ensemble launch is the fused eval");
+  // the launch's parameters: the kernel argument itself, or (ENS) a copy with the member's table and scalars
+  BlksegParams spm;
+  int ens_p = blockIdx.x;
+  if constexpr (ENS) {
+    const int v = blockIdx.x, Ee = sp_.E;
+    ens_p = v / Ee;
+    const int e = v - ens_p * Ee;
+    spm = sp_;
+    const double* const q = sp_.ens + 9 * (size_t)e;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {
+      spm.rad[j] = seg_uniform(q[j]);
+      spm.mur[j] = seg_uniform(q[3 + j]);
+      spm.mui[j] = seg_uniform(q[6 + j]);
+    }
+    spm.gtab = sp_.gtab + (size_t)e * 3 * NB * NB * bk.nblk;
+    spm.u_copy = e == 0 ? sp_.u_copy : nullptr;
+    spm.u_copy2 = nullptr;
+    spm.J2 = nullptr;
+    spm.coef2 = nullptr;
+    spm.done = nullptr;
+  }
+  const BlksegParams& sp = ENS ? spm : sp_;
+  const int bp = ENS ? ens_p : (int)blockIdx.x;  // the pulse: the row of u, of its copy and of a per-seed x_0
   if constexpr (MODE == BLKSEG_BWD) {  // a stale u (the check queued before this launch): leave every output alone
     if (sp.stale && *sp.stale != 0) return;
   }
@@ -958,9 +1000,9 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
   // lane's block and its first two slices of u (at cavity size that is all there is); then the LDS stores, and what
   // longer arrays have left in plain loops.
   const int ntab = 3 * E * nblk;
-  const double2* const x0g = reinterpret_cast<const double2*>(g.x0) + (g.x0_per_seed ? (size_t)b * Nm : 0);
+  const double2* const x0g = reinterpret_cast<const double2*>(g.x0) + (g.x0_per_seed ? (size_t)bp * Nm : 0);
   const double2* const xtg = reinterpret_cast<const double2*>(g.Xt);
-  const double* ub = sp.u + (size_t)b * Nt * nu;
+  const double* ub = sp.u + (size_t)bp * Nt * nu;
   // two controls in an aligned buffer: one 16-byte load per slice
   const bool u16 = nu == 2 && (reinterpret_cast<size_t>(ub) & 15) == 0;
   auto load_u = [&](int k) -> double2 {
@@ -1010,8 +1052,8 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
     const double u1 = uk.x, u2 = uk.y;
     for (int j = 0; j < nu; ++j) {
       const double v = j ? u2 : u1;
-      if (sp.u_copy) sp.u_copy[((size_t)b * Nt + k) * nu + j] = v;
-      if (sp.u_copy2) sp.u_copy2[((size_t)b * Nt + k) * nu + j] = v;
+      if (sp.u_copy) sp.u_copy[((size_t)bp * Nt + k) * nu + j] = v;
+      if (sp.u_copy2) sp.u_copy2[((size_t)bp * Nt + k) * nu + j] = v;
     }
     rmax = fmax(rmax, fma(fabs(u2), sp.rad[2], fma(fabs(u1), sp.rad[1], sp.rad[0])));
     double2* r = reinterpret_cast<double2*>(rec + 4 * (size_t)k);
@@ -1551,7 +1593,7 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
 #endif
   const bool early = W <= 4;
   auto publish = [&]() {
-    if (w != 0 || !sp.done) return;
+    if (ENS || w != 0 || !sp.done) return;
     unsigned int prev = 0;
     if (l == 0) {
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");  // the sc1 J store has reached memory
@@ -1936,6 +1978,45 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
   BK_T(t5);
   BK_ADD(4, t5 - t4);
   BK_ADD(5, t5 - t0);
+}
+
+// The weighted sums of an ensemble launch (k_blkseg_eval's ENS instantiations): dJdu[p][i] = Σ_e w_e g[p E + e][i] and
+// J[p] = Σ_e w_e Jm[p E + e], the members of pulse p being adjacent rows of g.  One thread per output element (VEC:
+// per pair of them, 16-byte loads and stores: n even, 16-byte aligned buffers); the members are added in ascending e
+// as acc = fma(w_e, v_e, acc) from 0, without atomics, so the result does not depend on scheduling.  The first B
+// threads also sum the costs (J2: the caller's copy, or nullptr).  n = Nt nu; Jm stays as it is (the member costs).
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_ens_reduce(int B, int E, int n, const double* __restrict__ w,
+                                                    const double* __restrict__ g, const double* __restrict__ Jm,
+                                                    double* __restrict__ dJdu, double* __restrict__ J,
+                                                    double* __restrict__ J2) {
+  const int nv = VEC ? n / 2 : n;
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx < (long long)B * nv) {
+    const int p = (int)(idx / nv), i = (int)(idx - (long long)p * nv);
+    if constexpr (VEC) {
+      const double2* src = reinterpret_cast<const double2*>(g + (size_t)p * E * n) + i;
+      double2 acc = make_double2(0.0, 0.0);
+      for (int e = 0; e < E; ++e) {
+        const double2 v = src[(size_t)e * nv];
+        const double we = w[e];
+        acc.x = fma(we, v.x, acc.x);
+        acc.y = fma(we, v.y, acc.y);
+      }
+      reinterpret_cast<double2*>(dJdu + (size_t)p * n)[i] = acc;
+    } else {
+      const double* src = g + (size_t)p * E * n + i;
+      double acc = 0.0;
+      for (int e = 0; e < E; ++e) acc = fma(w[e], src[(size_t)e * n], acc);
+      dJdu[(size_t)p * n + i] = acc;
+    }
+  }
+  if (idx < B) {
+    double acc = 0.0;
+    for (int e = 0; e < E; ++e) acc = fma(w[e], Jm[(size_t)idx * E + e], acc);
+    J[idx] = acc;
+    if (J2) J2[idx] = acc;
+  }
 }
 
 }  // namespace qoc

@@ -305,6 +305,27 @@ void herm_interval(const double* A, int N, double& lmin, double& lmax) {
 }
 
 // RCCL, resolved on first use (librccl.so.1 of the ROCm install).
+void gen_shift_bounds(const double* G, int N, double& mur, double& mui, double& rad) {
+  double lmin, lmax;
+  herm_interval(G, N, lmin, lmax);
+  const double cen = 0.5 * (lmin + lmax), scale = std::max(std::fabs(lmin), std::fabs(lmax));
+  mur = 0.0;
+  mui = -cen;
+  rad = 0.5 * (lmax - lmin) + 1e-13 * scale + 1e-300;  // Jacobi's error is ~N eps |H|
+}
+
+void gen_skew_test(const double* G, int N, bool& skew, bool& exact) {
+  double amax = 0.0, dev = 0.0;
+  for (int col = 0; col < N; ++col)
+    for (int row = 0; row < N; ++row) {
+      const size_t a = 2 * (row + (size_t)N * col), b = 2 * (col + (size_t)N * row);
+      amax = std::max(amax, std::hypot(G[a], G[a + 1]));
+      dev = std::max(dev, std::hypot(G[a] + G[b], G[a + 1] - G[b + 1]));  // |A + A^H|
+    }
+  skew = dev <= 1e-13 * std::max(amax, 1e-300);
+  exact = dev <= 4.0 * 2.220446049250313e-16 * amax;  // -i H dt of an exactly Hermitian H: dev = 0
+}
+
 RcclApi& rccl() {
   static RcclApi api;
   static bool tried = false;
@@ -417,6 +438,40 @@ int check_ready(qoc_ctx* c) {
   if (!c->have_cost) return fail(c, QOC_ERR_STATE, "cost not set (qoc_set_cost)");
   HIPCHK(c, hipSetDevice(c->dev));
   return QOC_OK;
+}
+
+// With a generator ensemble set (qoc_set_generator_ensemble) only qoc_eval_dev and what is built on it run: state and
+// co-state are per member, and the split call form is not part of the ensemble eval.
+static int ens_barred(qoc_ctx* c, const char* what) {
+  return fail(c, QOC_ERR_UNSUPPORTED,
+              "%s is not available while a generator ensemble is set (states and co-states are per member); "
+              "qoc_eval_dev and its callers are",
+              what);
+}
+// what qoc_eval_dev refuses under an ensemble, before anything on the context changes
+static int ens_eval_check(qoc_ctx* c, int order) {
+  if (!c->ens_E) return QOC_OK;
+  if (order < 0 || order > 4) return fail(c, QOC_ERR_ARG, "dUkdp_order must be 1..4 or QOC_DUKDP_EXACT (got %d)", order);
+  if (!c->concurrent || !blkseg_ens_ok(c, order))
+    return fail(c, QOC_ERR_UNSUPPORTED,
+                "the generator ensemble runs on the one-launch segmented eval only (blocks of 2-3 rows, fp64, TRACE / "
+                "ZCAL, no co-state source, no packing, the state penalty on blocks of 2 rows)");
+  return QOC_OK;
+}
+// drops the ensemble and its workspace (the stream is drained first: a queued eval may still read them)
+static void ens_clear(qoc_ctx* c) {
+  if (!c->ens_E && !c->ens_bytes) return;
+  if (c->stream) hipStreamSynchronize(c->stream);
+  for (void* p : {(void*)c->d_ens_gtab, (void*)c->d_ens_prm, (void*)c->d_ens_w, (void*)c->d_ens_J, (void*)c->d_ens_coef,
+                  (void*)c->d_ens_g})
+    if (p) hipFree(p);
+  c->d_ens_gtab = nullptr;
+  c->d_ens_prm = c->d_ens_w = c->d_ens_J = c->d_ens_g = nullptr;
+  c->d_ens_coef = nullptr;
+  c->dev_bytes -= c->ens_bytes;
+  c->ens_bytes = 0;
+  c->ens_E = 0;
+  c->ens_costs = false;
 }
 
 }  // namespace qoc_host
@@ -580,6 +635,7 @@ void qoc_destroy(qoc_ctx* c) {
   if (c->d_dead_rows) hipFree(c->d_dead_rows);
   if (c->d_gc_part) hipFree(c->d_gc_part);
   if (c->d_gseg) hipFree(c->d_gseg);
+  ens_clear(c);
   if (c->d_blkp_ctab) hipFree(c->d_blkp_ctab);
   if (c->d_blkp_M) hipFree(c->d_blkp_M);
   if (c->d_blkp_ph) hipFree(c->d_blkp_ph);
@@ -635,6 +691,7 @@ int qoc_set_generators(qoc_ctx* c, const double* A0, const double* const* Aj) {
       return fail(c, QOC_ERR_ARG, "generators couple the two compress_states row blocks");
     }
   }
+  ens_clear(c);  // a generator ensemble belongs to the nominal set it was checked against
   int r = upload(c, A0, c->d_A, NN);
   for (int j = 0; j < c->nu && r == QOC_OK; ++j) {
     if (!Aj[j]) return fail(c, QOC_ERR_ARG, "A[%d] is null", j);
@@ -688,16 +745,9 @@ int qoc_set_generators(qoc_ctx* c, const double* A0, const double* const* Aj) {
     // Ã_k = -i H̃_k has its spectrum on the imaginary axis within the bound ρ_k
     bool skew = true, exact = true;
     for (int j = 0; j <= c->nu && skew; ++j) {
-      const double* G = j == 0 ? A0 : Aj[j - 1];
-      double amax = 0.0, dev = 0.0;
-      for (int col = 0; col < c->N; ++col)
-        for (int row = 0; row < c->N; ++row) {
-          const size_t a = 2 * (row + (size_t)c->N * col), b = 2 * (col + (size_t)c->N * row);
-          amax = std::max(amax, std::hypot(G[a], G[a + 1]));
-          dev = std::max(dev, std::hypot(G[a] + G[b], G[a + 1] - G[b + 1]));  // |A + A^H|
-        }
-      skew = dev <= 1e-13 * std::max(amax, 1e-300);
-      exact = exact && dev <= 4.0 * 2.220446049250313e-16 * amax;  // -i H dt of an exactly Hermitian H: dev = 0
+      bool ex = true;
+      gen_skew_test(j == 0 ? A0 : Aj[j - 1], c->N, skew, ex);
+      exact = exact && ex;
     }
     c->skew_exact = skew && exact;
     std::vector<double> sh(2 * NN);
@@ -708,12 +758,7 @@ int qoc_set_generators(qoc_ctx* c, const double* A0, const double* const* Aj) {
         // the centre of H_j's spectral interval [λmin, λmax] (H_j = i A_j): Ã_j = -i (H_j - c_j I), and by Weyl's
         // inequality every H̃_k = Σ_j u_jk (H_j - c_j I) has its spectrum within ±(r_0 + Σ_j |u_jk| r_j),
         // r_j = (λmax - λmin) / 2 — the Chebyshev interval, tighter than the 1-norm (tunable bus: ρ 14.2 vs 19.5)
-        double lmin, lmax;
-        herm_interval(G, c->N, lmin, lmax);
-        const double cen = 0.5 * (lmin + lmax), scale = std::max(std::fabs(lmin), std::fabs(lmax));
-        mr = 0.0;
-        mi = -cen;
-        c->tprm.rad[j] = 0.5 * (lmax - lmin) + 1e-13 * scale + 1e-300;  // Jacobi's error is ~N eps |H|
+        gen_shift_bounds(G, c->N, mr, mi, c->tprm.rad[j]);
       }
       std::memcpy(sh.data(), G, 2 * NN * sizeof(double));
       if (!skew) {
@@ -772,6 +817,116 @@ int qoc_set_generators(qoc_ctx* c, const double* A0, const double* const* Aj) {
   }
   c->have_gen = true;
   c->fwd.valid = false;
+  return QOC_OK;
+}
+
+int qoc_set_generator_ensemble(qoc_ctx* c, int E, const double* A0s, const double* const* Ajs, const double* weights) {
+  if (!c) return fail(nullptr, QOC_ERR_ARG, "null context");
+  if (E < 0) return fail(c, QOC_ERR_ARG, "E must be >= 0 (got %d)", E);
+  HIPCHK(c, hipSetDevice(c->dev));
+  if (E == 0) {
+    if (!c->ens_E) return QOC_OK;
+    ens_clear(c);
+    c->fwd.valid = false;
+    return QOC_OK;
+  }
+  if (!c->have_gen) return fail(c, QOC_ERR_STATE, "generators not set (qoc_set_generators comes first)");
+  if (!A0s || !Ajs) return fail(c, QOC_ERR_ARG, "null argument");
+  for (int j = 0; j < c->nu; ++j)
+    if (!Ajs[j]) return fail(c, QOC_ERR_ARG, "Ajs[%d] is null", j);
+  const int N = c->N, NB = c->blk_nb, nblk = c->nblk;
+  if ((NB != 2 && NB != 3) || !c->skew_exact || c->nu > 2 || (int)c->h_brow.size() != nblk * NB)
+    return fail(c, QOC_ERR_UNSUPPORTED,
+                "a generator ensemble needs the segmented eval's layout: exactly skew-Hermitian generators with "
+                "invariant blocks of 2 or 3 rows");
+  if ((long long)c->B * E > (1ll << 30)) return fail(c, QOC_ERR_ARG, "B x E = %lld workgroups", (long long)c->B * E);
+  const size_t NN = (size_t)N * N;
+  std::vector<int> blk_of(N, -1);
+  for (int q = 0; q < nblk * NB; ++q)
+    if (c->h_brow[q] >= 0) blk_of[c->h_brow[q]] = q / NB;
+  std::vector<double> w(E, 1.0 / E);
+  if (weights) {
+    double sum = 0.0;
+    for (int e = 0; e < E; ++e) {
+      if (!std::isfinite(weights[e]) || weights[e] < 0.0)
+        return fail(c, QOC_ERR_ARG, "weights[%d] = %g: weights must be finite and >= 0", e, weights[e]);
+      w[e] = weights[e];
+      sum += weights[e];
+    }
+    if (!(sum > 0.0) || !std::isfinite(sum)) return fail(c, QOC_ERR_ARG, "the weights must have a positive sum");
+  }
+  const size_t tabn = (size_t)nblk * 3 * NB * NB * 2;
+  std::vector<double> tabs(tabn * E), prm((size_t)9 * E, 0.0), gen((size_t)(c->nu + 1) * 2 * NN);
+  for (int e = 0; e < E; ++e) {
+    for (int j = 0; j <= c->nu; ++j) {
+      const double* G = (j == 0 ? A0s : Ajs[j - 1]) + (size_t)e * 2 * NN;
+      bool skew = false, exact = false;
+      gen_skew_test(G, N, skew, exact);
+      if (!skew || !exact)
+        return fail(c, QOC_ERR_ARG, "member %d: generator %d is not exactly skew-Hermitian", e, j);
+      for (int col = 0; col < N; ++col)
+        for (int row = 0; row < N; ++row) {
+          const double* v = G + 2 * (row + (size_t)N * col);
+          if (!std::isfinite(v[0]) || !std::isfinite(v[1]))
+            return fail(c, QOC_ERR_ARG, "member %d: generator %d has a non-finite entry", e, j);
+          if (row != col && (v[0] != 0.0 || v[1] != 0.0) && blk_of[row] != blk_of[col])
+            return fail(c, QOC_ERR_ARG, "member %d: generator %d couples rows %d and %d, which the nominal set keeps in "
+                        "different blocks", e, j, row, col);
+        }
+      std::memcpy(gen.data() + (size_t)j * 2 * NN, G, 2 * NN * sizeof(double));
+      gen_shift_bounds(G, N, prm[9 * e + 3 + j], prm[9 * e + 6 + j], prm[9 * e + j]);
+    }
+    blk_gen_table(c, c->h_brow, NB, nblk, gen.data(), &prm[9 * e + 3], &prm[9 * e + 6], tabs.data() + tabn * e);
+  }
+  // lazily kept states / co-states are rebuilt with the context as it is (an ensemble eval keeps nothing lazy)
+  if (int r0 = blk_materialize(c)) return r0;
+  // the new ensemble's buffers first, so that a failed allocation leaves the context as it was
+  const size_t BE = (size_t)c->B * E;
+  const size_t bytes[6] = {tabs.size() * sizeof(double), prm.size() * sizeof(double), (size_t)E * sizeof(double),
+                           BE * sizeof(double), BE * 2 * c->m_user * sizeof(cx<double>),
+                           BE * c->Nt * c->nu * sizeof(double)};
+  void* buf[6] = {};
+  size_t total = 0;
+  for (int i = 0; i < 6; ++i) {
+    const hipError_t e_ = hipMalloc(&buf[i], bytes[i]);
+    if (e_ != hipSuccess) {
+      for (int q = 0; q < i; ++q) hipFree(buf[q]);
+      return fail(c, QOC_ERR_HIP, "the ensemble's workspace (%zu bytes): %s", bytes[i], hipGetErrorString(e_));
+    }
+    total += bytes[i];
+  }
+  hipError_t e_ = hipMemcpy(buf[0], tabs.data(), bytes[0], hipMemcpyHostToDevice);
+  if (e_ == hipSuccess) e_ = hipMemcpy(buf[1], prm.data(), bytes[1], hipMemcpyHostToDevice);
+  if (e_ == hipSuccess) e_ = hipMemcpy(buf[2], w.data(), bytes[2], hipMemcpyHostToDevice);
+  if (e_ != hipSuccess) {
+    for (void* p : buf) hipFree(p);
+    return fail(c, QOC_ERR_HIP, "the ensemble's tables: %s", hipGetErrorString(e_));
+  }
+  ens_clear(c);
+  c->d_ens_gtab = (double2*)buf[0];
+  c->d_ens_prm = (double*)buf[1];
+  c->d_ens_w = (double*)buf[2];
+  c->d_ens_J = (double*)buf[3];
+  c->d_ens_coef = (cx<double>*)buf[4];
+  c->d_ens_g = (double*)buf[5];
+  c->ens_bytes = total;
+  c->dev_bytes += total;
+  c->ens_E = E;
+  c->fwd.valid = false;  // states are per member from here on
+  return QOC_OK;
+}
+
+int qoc_ensemble_size(qoc_ctx* c) { return c ? c->ens_E : 0; }
+
+double* qoc_member_costs_dev(qoc_ctx* c) { return c && c->ens_E ? c->d_ens_J : nullptr; }
+
+int qoc_get_member_costs(qoc_ctx* c, double* Jm) {
+  if (!c || !Jm) return fail(c, QOC_ERR_ARG, "null argument");
+  if (!c->ens_E) return fail(c, QOC_ERR_STATE, "no generator ensemble is set");
+  if (!c->ens_costs) return fail(c, QOC_ERR_STATE, "no eval since the ensemble was set");
+  HIPCHK(c, hipSetDevice(c->dev));
+  HIPCHK(c, hipMemcpyAsync(Jm, c->d_ens_J, (size_t)c->B * c->ens_E * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return QOC_OK;
 }
 
@@ -969,6 +1124,7 @@ int qoc_set_compression(qoc_ctx* c, const int* rows1, int nr1, const int* cols1,
 }
 
 int qoc_propagate_dev(qoc_ctx* c, const double* d_u, double* d_J) {
+  if (c && c->ens_E) return ens_barred(c, "qoc_propagate_dev");
   int r = check_ready(c);
   if (r) return r;
   if (!d_u) return fail(c, QOC_ERR_ARG, "d_u is null");
@@ -977,6 +1133,7 @@ int qoc_propagate_dev(qoc_ctx* c, const double* d_u, double* d_J) {
 }
 
 int qoc_grape_sensitivity_dev(qoc_ctx* c, const double* d_u, int order, double* d_dJdu) {
+  if (c && c->ens_E) return ens_barred(c, "qoc_grape_sensitivity_dev");
   int r = check_ready(c);
   if (r) return r;
   if (!c->fwd.valid) return fail(c, QOC_ERR_STATE, "grape_sensitivity called before propagate");
@@ -1007,6 +1164,18 @@ int qoc_eval_dev(qoc_ctx* c, const double* d_u, int order, double* d_J, double* 
   if (r) return r;
   if (!d_u) return fail(c, QOC_ERR_ARG, "d_u is null");
   double* const out = d_dJdu ? d_dJdu : c->d_dJdu;
+  if (c->ens_E) {
+    // a generator ensemble: one workgroup of the segmented eval per (pulse, member), then the weighted sums.  States
+    // and co-states are per member and none is kept: the forward stays invalid, the last backward's record stands, and
+    // qoc_allgather_best picks from the J̄ in d_J.
+    if ((r = ens_eval_check(c, order))) return r;
+    forward_begin(c);
+    if ((r = blkseg_eval_ens(c, order, d_u, d_J, out))) return r;
+    c->props_since_reset++;
+    c->h_u.clear();
+    c->h_coef.clear();
+    return QOC_OK;
+  }
   if (c->concurrent && blkseg_ok(c, order)) {
     // block propagators with the time axis in segments: one launch reads u (and copies it to d_u) and writes J and
     // dJdu; x_k and λ_k are rebuilt on demand (qoc_blkseg.hpp)
@@ -1041,6 +1210,7 @@ int qoc_eval_dev(qoc_ctx* c, const double* d_u, int order, double* d_J, double* 
 }
 
 int qoc_propagate(qoc_ctx* c, const double* u, double* J_out) {
+  if (c && c->ens_E) return ens_barred(c, "qoc_propagate");
   int r = check_ready(c);
   if (r) return r;
   if (!u) return fail(c, QOC_ERR_ARG, "u is null");
@@ -1056,6 +1226,7 @@ int qoc_propagate(qoc_ctx* c, const double* u, double* J_out) {
 }
 
 int qoc_grape_sensitivity(qoc_ctx* c, const double* u, int order, const double* lambda_final, double* dJdu_out) {
+  if (c && c->ens_E) return ens_barred(c, "qoc_grape_sensitivity");
   int r = check_ready(c);
   if (r) return r;
   if (!c->fwd.valid) return fail(c, QOC_ERR_STATE, "grape_sensitivity called before propagate");
@@ -1238,6 +1409,7 @@ int qoc_eval_spline_dev(qoc_ctx* c, const double* d_c, int order, double* d_J, d
   if (c->cost_kind == QOC_COST_EXTERNAL)
     return fail(c, QOC_ERR_STATE, "qoc_eval_spline_dev needs a device-side cost (TRACE or ZCAL)");
   if (order < 0 || order > 4) return fail(c, QOC_ERR_ARG, "dUkdp_order must be 1..4 or QOC_DUKDP_EXACT (got %d)", order);
+  if ((r = ens_eval_check(c, order))) return r;
   const long long nuT = (long long)c->B * c->Nt * c->nu;
   const unsigned blocks = (unsigned)std::min<long long>((nuT + 255) / 256, 4096);
   hipLaunchKernelGGL(k_spline_u, dim3(blocks), dim3(256), 0, c->stream, c->B, c->Nt, c->ns, c->nu, c->d_Bs, d_c,
@@ -1273,6 +1445,7 @@ int qoc_eval_spline(qoc_ctx* c, const double* coef, int order, double* J_out, do
 
 int qoc_propagate_spline(qoc_ctx* c, const double* coef, double* J_out) {
   if (!c) return fail(nullptr, QOC_ERR_ARG, "null context");
+  if (c->ens_E) return ens_barred(c, "qoc_propagate_spline");
   if (!c->ns) return fail(c, QOC_ERR_STATE, "spline basis not set (qoc_set_spline_basis)");
   if (!coef) return fail(c, QOC_ERR_ARG, "c is null");
   HIPCHK(c, hipSetDevice(c->dev));
@@ -1294,6 +1467,7 @@ int qoc_propagate_spline(qoc_ctx* c, const double* coef, double* J_out) {
 
 int qoc_sensitivity_spline(qoc_ctx* c, const double* coef, int order, double* dJdc_out) {
   if (!c) return fail(nullptr, QOC_ERR_ARG, "null context");
+  if (c->ens_E) return ens_barred(c, "qoc_sensitivity_spline");
   if (!c->ns) return fail(c, QOC_ERR_STATE, "spline basis not set (qoc_set_spline_basis)");
   if (!coef) return fail(c, QOC_ERR_ARG, "c is null");
   int r = check_ready(c);
@@ -1345,6 +1519,7 @@ int qoc_set_propagation(qoc_ctx* c, int method, int nsub) {
 
 int qoc_propagate_envelope(qoc_ctx* c, int kind, const double* params, int np, double tgate, double dt, double* J_out,
                            double* x_out) {
+  if (c && c->ens_E) return ens_barred(c, "qoc_propagate_envelope");
   int r = check_ready(c);
   if (r) return r;
   if (!params || np < 1 || np > 64) return fail(c, QOC_ERR_ARG, "bad parameter array");
@@ -1380,6 +1555,7 @@ int qoc_propagate_envelope(qoc_ctx* c, int kind, const double* params, int np, d
 // qoc_eval_envelope / _dev: qoc_propagate_envelope's argument checks, then what the adjoint does not cover
 static int env_eval_check(qoc_ctx* c, int kind, const void* params, int np, double tgate, double dt, const void* dJdp,
                           long long* nsteps) {
+  if (c && c->ens_E) return ens_barred(c, "qoc_eval_envelope");
   int r = check_ready(c);
   if (r) return r;
   if (!params || np < 1 || np > 64) return fail(c, QOC_ERR_ARG, "bad parameter array");

@@ -247,18 +247,32 @@ struct qoc_ctx {
   double2* d_gseg = nullptr;         // B x NB^2 x S x nblk complex: the segmented forward's G at every segment end (fwd.kind 1)
   size_t gseg_bytes = 0;
   // the segmented eval's launch shape, kept between evals: valid while the sizes it was derived from (seg_key: B, Nt,
-  // N, m, nu, block rows, blocks, penalised or not) are the context's; the QOC_BLKSEG_W / _S / _RB switches are read
+  // N, m, nu, block rows, blocks, penalised or not, ensemble members) are the context's; the QOC_BLKSEG_W / _S / _RB switches are read
   // when it is derived.  seg_attr[NB - 2][order - 1, exact: 4][mode][penalised]: this context has raised that k_blkseg_eval
   // instance's dynamic-LDS limit (blkseg_lds_attr)
   mutable BlksegShape seg_shape{};
-  mutable int seg_key[8] = {-1, -1, -1, -1, -1, -1, -1, -1};
+  mutable int seg_key[9] = {-1, -1, -1, -1, -1, -1, -1, -1, -1};
   bool seg_attr[2][5][3][2] = {};  // [..][penalised]; order slot 4: the exact instantiation (ORD 0)
+  bool seg_attr_ens[2][5][2] = {};  // the same for the ensemble instantiations (fused only)
   // the state penalty as the segmented eval takes it (blkseg_pen): per block row i a bit mask over the blocks
   // (seg_prow[i], bit β: row i of block β is in P) and a bit mask over the columns C; derived from h_pen_rows /
   // h_pen_cols and the block rows h_brow, invalidated by qoc_set_state_penalty and by a new block layout
   mutable bool seg_pen_valid = false;
   mutable unsigned int seg_prow[3] = {0, 0, 0}, seg_pcol = 0;
   std::vector<int> h_brow;           // nblk x blk_nb rows of each block (-1 padding), the host's copy of d_brow
+  // A generator ensemble (qoc_set_generator_ensemble): ens_E > 0 sets evaluated for every pulse, one workgroup of the
+  // segmented eval per (pulse, member) and k_ens_reduce behind it (qoc_blkseg.hpp).  The block layout stays the
+  // nominal set's.  Everything below is allocated by the setter, counted in dev_bytes (ens_bytes) and freed when the
+  // ensemble is cleared (E = 0, qoc_set_generators) and at qoc_destroy.
+  int ens_E = 0;
+  double2* d_ens_gtab = nullptr;     // [E][nblk][3][blk_nb^2]: the members' shifted generator blocks (blk_gen_table)
+  double* d_ens_prm = nullptr;       // E x 9: rad[3] | mur[3] | mui[3] of each member (gen_shift_bounds)
+  double* d_ens_w = nullptr;         // E weights, as given
+  double* d_ens_J = nullptr;         // B x E member costs of the last ensemble eval (qoc_member_costs_dev)
+  cx<double>* d_ens_coef = nullptr;  // B x E x 2m λ_N coefficients
+  double* d_ens_g = nullptr;         // B x E x Nt x nu member gradients
+  size_t ens_bytes = 0;
+  bool ens_costs = false;            // d_ens_J holds an eval's costs
   int* h_flag = nullptr;             // host-mapped stale-u flag of the queued check (k_compare_u_flags)
   int flag_turn = 0;                 // which of the two device flags d_flag[0 / 1] the next queued check writes
   hipEvent_t flag_ev = nullptr;      // recorded after that copy
@@ -386,6 +400,12 @@ int mark_begin(qoc_ctx* c, int phase, hipStream_t s = nullptr);
 void mark_end(qoc_ctx* c, int idx, hipStream_t s = nullptr);
 RcclApi& rccl();
 
+// the shift and bound of one exactly skew-Hermitian generator (N x N, column-major interleaved): μ = -i c with c the
+// centre of the spectral interval of H = i A, rad its half-width with the eigenvalue solver's margin
+void gen_shift_bounds(const double* G, int N, double& mur, double& mui, double& rad);
+// |A + A^H| of one generator against its largest entry: skew (Chebyshev's bar) and exact (the segmented eval's)
+void gen_skew_test(const double* G, int N, bool& skew, bool& exact);
+
 // ---- qoc_run_expm.hip ----
 bool expm_supported(int N, int prec);
 // alg 0: Padé + solve (reference algorithm); alg 1: register-resident Taylor T12; alg 2: LDS Paterson-Stockmeyer.
@@ -464,6 +484,10 @@ int tchain_prep(qoc_ctx* c);
 
 // ---- qoc_run_blk.hip ----
 int blk_detect(qoc_ctx* c);
+// the segmented eval's table of one generator set on the block rows brow (nblk x NB): [nblk][3][NB^2] complex into tab;
+// gen: (nu + 1) x N x N column-major interleaved, mur / mui: the shifts taken off the diagonals
+void blk_gen_table(const qoc_ctx* c, const std::vector<int>& brow, int NB, int nblk, const double* gen,
+                   const double* mur, const double* mui, double* tab);
 bool blk_active(const qoc_ctx* c);
 bool blk_rot(const qoc_ctx* c);
 bool blku_on(const qoc_ctx* c);  // blocks of <= 4 rows on block propagators (qoc_blku.hpp)
@@ -504,6 +528,10 @@ int blku_costates(qoc_ctx* c);  // qoc_get_costates after the fused block backwa
 // the segmented block eval (qoc_blkseg.hpp): one launch for J and dJdu, x_k / λ_k rebuilt on demand
 bool blkseg_ok(const qoc_ctx* c, int order);
 int blkseg_eval(qoc_ctx* c, int order, const double* d_u, double* d_J, double* d_dJdu);
+// with a generator ensemble set: whether the fused launch takes the eval (blkseg_ok, and not the two-launch penalised
+// form of blocks of 3 rows); the eval itself: B E workgroups, then k_ens_reduce into d_J / the caller's J and d_dJdu
+bool blkseg_ens_ok(const qoc_ctx* c, int order);
+int blkseg_eval_ens(qoc_ctx* c, int order, const double* d_u, double* d_J, double* d_dJdu);
 // the reference's split call form on the segmented eval: propagate = phases 0-2 (G at the segment ends to HBM),
 // grape_sensitivity = phase 3 (stale: the device flag of a stale-u check queued before it, or nullptr)
 bool blkseg_split_ok(const qoc_ctx* c);

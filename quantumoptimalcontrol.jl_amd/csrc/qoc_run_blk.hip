@@ -128,18 +128,8 @@ int blk_detect(qoc_ctx* c) {
     // the segmented eval's generator blocks, block-major [nblk][3][NB^2]: the entries of the shifted generators
     // Ã_j = A_j - μ_j I (the values qoc_set_generators uploads to d_At: the same subtraction) on each block's rows,
     // zero for j > nu and for a padded row; its prologue copies the table instead of gathering through d_brow
-    const int E = NB * NB;
-    std::vector<double> tab((size_t)nblk * 3 * E * 2, 0.0);
-    for (int b = 0; b < nblk; ++b)
-      for (int j = 0; j <= c->nu && j < 3; ++j)
-        for (int e = 0; e < E; ++e) {
-          const int ri = brow[(size_t)b * NB + e / NB], rk = brow[(size_t)b * NB + e % NB];
-          if (ri < 0 || rk < 0) continue;
-          const double* v = c->h_gen.data() + 2 * (j * NN + ri + (size_t)N * rk);
-          double* t = tab.data() + 2 * (((size_t)b * 3 + j) * E + e);
-          t[0] = ri == rk ? v[0] - c->tprm.mur[j] : v[0];
-          t[1] = ri == rk ? v[1] - c->tprm.mui[j] : v[1];
-        }
+    std::vector<double> tab((size_t)nblk * 3 * NB * NB * 2, 0.0);
+    blk_gen_table(c, brow, NB, nblk, c->h_gen.data(), c->tprm.mur, c->tprm.mui, tab.data());
     HIPCHK(c, hipMalloc((void**)&c->d_gtab, tab.size() * sizeof(double)));
     HIPCHK(c, hipMemcpy(c->d_gtab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
     c->blk_dev_bytes += tab.size() * sizeof(double);
@@ -156,6 +146,23 @@ int blk_detect(qoc_ctx* c) {
   c->blk_real = real;
   c->nwb = (int)(wrow.size() / 16);
   return QOC_OK;
+}
+
+void blk_gen_table(const qoc_ctx* c, const std::vector<int>& brow, int NB, int nblk, const double* gen,
+                   const double* mur, const double* mui, double* tab) {
+  const int N = c->N, E = NB * NB;
+  const size_t NN = (size_t)N * N;
+  std::fill(tab, tab + (size_t)nblk * 3 * E * 2, 0.0);
+  for (int b = 0; b < nblk; ++b)
+    for (int j = 0; j <= c->nu && j < 3; ++j)
+      for (int e = 0; e < E; ++e) {
+        const int ri = brow[(size_t)b * NB + e / NB], rk = brow[(size_t)b * NB + e % NB];
+        if (ri < 0 || rk < 0) continue;
+        const double* v = gen + 2 * (j * NN + ri + (size_t)N * rk);
+        double* t = tab + 2 * (((size_t)b * 3 + j) * E + e);
+        t[0] = ri == rk ? v[0] - mur[j] : v[0];
+        t[1] = ri == rk ? v[1] - mui[j] : v[1];
+      }
 }
 
 // The block path runs the Taylor-action chains' fp64 scheme (step records, shifted generators) on unpacked states

@@ -12,7 +12,8 @@ namespace qoc_host {
 // kernel's <= 256 VGPRs), UPW = 64 / nblk segments per wave, S = W UPW segments of L = ceil(Nt / S) slices (then S
 // trimmed so that no segment is empty).  QOC_BLKSEG_W / QOC_BLKSEG_S override the waves / cap the segments.
 // Derived once per context and again when one of its inputs changes (qoc_ctx::seg_key): every eval asks for it, some
-// twice, and the B = 1 plumbing latency is host time.  The sizes are compared here, not invalidated by their setters:
+// twice, and the B = 1 plumbing latency is host time.  With a generator ensemble set the launch has B E workgroups, which
+// is what the waves-per-workgroup rule counts, and E is part of the key.  The sizes are compared here, not invalidated by their setters:
 // m moves with the state packing and the blocks with every qoc_set_generators, and a missed setter would launch a
 // stale shape.  The cache is the context's (mutable members: blkseg_ok, a predicate on a const context, fills it
 // too); like the rest of a context it is for one host thread at a time.  The reference returned stays valid until
@@ -39,12 +40,17 @@ static bool blkseg_pen(const qoc_ctx* c) {
 
 static const BlksegShape& blkseg_shape(const qoc_ctx* c) {
   const bool pen = blkseg_pen(c);
-  const int key[8] = {c->B, c->Nt, c->N, c->m, c->nu, c->blk_nb, c->nblk, pen ? 1 : 0};
-  if (std::equal(key, key + 8, c->seg_key)) return c->seg_shape;
+  const int key[9] = {c->B, c->Nt, c->N, c->m, c->nu, c->blk_nb, c->nblk, pen ? 1 : 0, c->ens_E};
+  if (std::equal(key, key + 9, c->seg_key)) return c->seg_shape;
   BlksegShape& s = c->seg_shape;
   s = BlksegShape{};
-  const int per_cu = std::max(1, std::min(8, (c->B + c->ncu - 1) / std::max(1, c->ncu)));
-  s.W = std::max(1, std::min(8, env_int("QOC_BLKSEG_W", 8 / per_cu)));
+  const long long wgs = (long long)c->B * std::max(1, c->ens_E);
+  const int per_cu = (int)std::max<long long>(1, std::min<long long>(8, (wgs + c->ncu - 1) / std::max(1, c->ncu)));
+  // ensemble launches keep at least 4 waves: at 8 workgroups per CU (B E = 2048; cavity Nt = 1000 and zz Nt = 500, order 3
+  // and exact) 4 waves measured 1.5-1.8 x the rule's single wave and 1.1-1.4 x two ("Ensemble evals"); the
+  // plain eval's rule is untouched
+  const int wdef = c->ens_E > 0 ? std::max(4, 8 / per_cu) : 8 / per_cu;
+  s.W = std::max(1, std::min(8, env_int("QOC_BLKSEG_W", wdef)));
   s.UPW = 64 / std::max(1, c->nblk);
   int S = std::max(1, std::min(s.W * s.UPW, c->Nt));
   S = std::max(1, std::min(S, env_int("QOC_BLKSEG_S", S)));
@@ -61,7 +67,7 @@ static const BlksegShape& blkseg_shape(const qoc_ctx* c) {
   }
   if (env_set("QOC_BLKSEG_RB")) s.RB = std::max(1, std::min(env_int("QOC_BLKSEG_RB", 0), rbmax));
   s.lds = blkseg_lds(c->N, c->m, c->nu, c->blk_nb, c->nblk, c->Nt, s.S, s.W, s.RB, pen);
-  std::copy(key, key + 8, c->seg_key);
+  std::copy(key, key + 9, c->seg_key);
   return s;
 }
 
@@ -164,6 +170,40 @@ static hipError_t blkseg_lds_attr(qoc_ctx* c, int nb, int ord, int mode, bool pe
   return e;
 }
 
+// the ensemble launch: B E workgroups of the fused kernel's ENS instantiation, J and the coefficients into the
+// ensemble's workspace (sp.dJdu is the caller's to point there)
+static hipError_t blkseg_launch_ens(qoc_ctx* c, int order, const BlksegShape& s, const BlksegParams& sp) {
+  TChainArgs g = tchain_args(c);
+  g.J = c->d_ens_J;
+  g.coef = c->d_ens_coef;
+  const BlkArgs bk = blk_args(c);
+  return blkseg_dispatch(c->blk_nb, order, [&](auto NB_, auto ORD_) {
+    constexpr int NB = decltype(NB_)::value, ORD = decltype(ORD_)::value;
+    auto launch = [&](auto PEN_) {
+      constexpr bool PEN = decltype(PEN_)::value;
+      if constexpr (PEN && NB == 3) {  // (the two-launch form: blkseg_ens_ok declines)
+        return hipErrorInvalidValue;
+      } else {
+        auto kern = k_blkseg_eval<NB, ORD, 8, BLKSEG_FUSED, PEN, true>;
+        bool& set = c->seg_attr_ens[NB - 2][ORD == 0 ? BLK_ORDMAX : ORD - 1][PEN ? 1 : 0];
+        if (s.lds > 65536 && !set) {
+          hipFuncAttributes fa{};
+          hipError_t e = hipFuncGetAttributes(&fa, (const void*)kern);
+          if (e != hipSuccess) return e;
+          e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  (int)(BLKSEG_LDS_MAX - fa.sharedSizeBytes));
+          if (e != hipSuccess) return e;
+          set = true;
+        }
+        hipLaunchKernelGGL(kern, dim3((unsigned)(c->B * c->ens_E)), dim3(64 * s.W), s.lds, c->stream, g, bk, sp);
+        return hipGetLastError();
+      }
+    };
+    if (sp.pen_mu != 0.0) return launch(std::true_type());
+    return launch(std::false_type());
+  });
+}
+
 template <int MODE>
 static hipError_t blkseg_launch(qoc_ctx* c, int order, const BlksegShape& s, const BlksegParams& sp) {
   const TChainArgs g = tchain_args(c);
@@ -226,6 +266,51 @@ int blkseg_eval(qoc_ctx* c, int order, const double* d_u, double* d_J, double* d
   c->bwd.lazy = true;
   c->bwd.route = 6;
   c->jbest.ready = true;
+  return QOC_OK;
+}
+
+bool blkseg_ens_ok(const qoc_ctx* c, int order) {
+  if (c->ens_E < 1 || !blkseg_ok(c, order)) return false;
+  return !(blkseg_pen(c) && c->blk_nb == 3);  // (G and D per seed through HBM: not part of the ensemble eval)
+}
+
+// One eval of every pulse over the ensemble: the fused kernel on B E (pulse, member) workgroups writes the members'
+// J, coefficients and dJdu into the ensemble's workspace (and u into d_u, by member 0's workgroups, when the caller's
+// buffer is another one), then k_ens_reduce forms the weighted sums in d_J (and the caller's J) and d_dJdu.  Nothing
+// lazy is kept and the best-pair epilogue is off: k_argmin_seed picks from d_J.
+int blkseg_eval_ens(qoc_ctx* c, int order, const double* d_u, double* d_J, double* d_dJdu) {
+  const BlksegShape s = blkseg_shape(c);
+  BlksegParams sp;
+  int r = blkseg_params(c, s, sp);
+  if (r) return r;
+  sp.u = d_u;
+  sp.u_copy = d_u != c->d_u ? c->d_u : nullptr;
+  sp.dJdu = c->d_ens_g;
+  sp.done = nullptr;
+  sp.best = sp.best_res = sp.best_out = nullptr;
+  sp.gtab = c->d_ens_gtab;
+  sp.E = c->ens_E;
+  sp.ens = c->d_ens_prm;
+  c->jbest.direct = false;
+  const int mk = mark_begin(c, 2);
+  hipError_t e = blkseg_launch_ens(c, order, s, sp);
+  if (e == hipSuccess) {
+    const int n = c->Nt * c->nu;
+    const bool vec = c->nu == 2 && (reinterpret_cast<size_t>(d_dJdu) & 15) == 0;
+    const long long thr = std::max<long long>((long long)c->B * (vec ? n / 2 : n), c->B);
+    const unsigned grid = (unsigned)((thr + 255) / 256);
+    double* const J2 = d_J && d_J != c->d_J ? d_J : nullptr;
+    if (vec)
+      hipLaunchKernelGGL(k_ens_reduce<true>, dim3(grid), dim3(256), 0, c->stream, c->B, c->ens_E, n, c->d_ens_w,
+                         c->d_ens_g, c->d_ens_J, d_dJdu, c->d_J, J2);
+    else
+      hipLaunchKernelGGL(k_ens_reduce<false>, dim3(grid), dim3(256), 0, c->stream, c->B, c->ens_E, n, c->d_ens_w,
+                         c->d_ens_g, c->d_ens_J, d_dJdu, c->d_J, J2);
+    e = hipGetLastError();
+  }
+  mark_end(c, mk);
+  if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "k_blkseg_eval (ensemble) launch: %s", hipGetErrorString(e));
+  c->ens_costs = true;
   return QOC_OK;
 }
 

@@ -105,6 +105,54 @@ function upload!(c::MI355XCache, A0, A, x0)
     end
 end
 
+"""
+    set_generator_ensemble!(cache, A0s, As, weights=nothing)
+
+Robust control (include/qoc.h `qoc_set_generator_ensemble`): `A0s[e]` and `As[j][e]` are member e's Δt-prescaled
+generators (E members, the layout of `upload!`'s arguments per member); `weights` E values used as given (`nothing`:
+1/E each); an empty `A0s` clears the ensemble.  The generators of the last `propagate` (the nominal set) fix the block
+layout, so call it after one.  With an ensemble set the library evaluates J̄ = Σ_e w_e J(u; member e) in
+`qoc_eval_dev` / `qoc_eval_spline` (built-in costs: set one with `qoc_set_cost`, this cache's default is the external
+cost of the reference's closures) and refuses `propagate` / `grape_sensitivity`, whose states are per member.
+`upload!` of other generators (any later `propagate` after clearing) drops it.  Like the rest of this shim it is
+written against the ABI and has not been run (no `julia` where the library is built and tested).
+"""
+function set_generator_ensemble!(c::MI355XCache, A0s::Vector{<:AbstractMatrix}, As::Vector{<:Vector},
+                                 weights::Union{Nothing,AbstractVector}=nothing)
+    E = length(A0s)
+    if E == 0
+        check(ccall((:qoc_set_generator_ensemble, libqoc), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{ComplexF64}, Ptr{Ptr{ComplexF64}}, Ptr{Cdouble}),
+                    c.ctx, 0, C_NULL, C_NULL, C_NULL), c.ctx)
+        return nothing
+    end
+    length(As) == c.nu || error("expected $(c.nu) stacks of control generators, got $(length(As))")
+    all(length(a) == E for a in As) || error("every stack of control generators needs $E members")
+    # members contiguous: N x N x E column-major is E matrices of N x N one after the other
+    A0c = cat((Matrix{ComplexF64}(a) for a in A0s)...; dims=3)
+    Ac = [cat((Matrix{ComplexF64}(a) for a in stack)...; dims=3) for stack in As]
+    ptrs = [pointer(a) for a in Ac]
+    w = weights === nothing ? nothing : Vector{Float64}(weights)
+    w === nothing || length(w) == E || error("weights needs $E entries")
+    GC.@preserve A0c Ac ptrs w begin
+        check(ccall((:qoc_set_generator_ensemble, libqoc), Cint,
+                    (Ptr{Cvoid}, Cint, Ptr{ComplexF64}, Ptr{Ptr{ComplexF64}}, Ptr{Cdouble}),
+                    c.ctx, E, A0c, ptrs, w === nothing ? C_NULL : pointer(w)), c.ctx)
+    end
+    c.gen = 0   # the next upload! reaches qoc_set_generators (which clears the ensemble) whatever its generators
+    return nothing
+end
+
+"""Members of the generator ensemble (0: none)."""
+ensemble_size(c::MI355XCache) = Int(ccall((:qoc_ensemble_size, libqoc), Cint, (Ptr{Cvoid},), c.ctx))
+
+"""J of every member for the cache's one pulse at the last ensemble eval (`qoc_get_member_costs`); not run, see above."""
+function member_costs(c::MI355XCache)
+    Jm = zeros(max(ensemble_size(c), 1))
+    check(ccall((:qoc_get_member_costs, libqoc), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), c.ctx, Jm), c.ctx)
+    return Jm
+end
+
 """States of the last propagate, fetched lazily (the reference returns cache.x, Nt+1 matrices)."""
 struct LazyStates <: AbstractVector{Matrix{ComplexF64}}
     c::MI355XCache

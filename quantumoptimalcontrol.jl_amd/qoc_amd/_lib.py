@@ -53,6 +53,10 @@ SIGNATURES = {
     "qoc_stream": (_vp, [_vp]),
     "qoc_synchronize": (C.c_int, [_vp]),
     "qoc_set_generators": (C.c_int, [_vp, _dp, C.POINTER(_dp)]),
+    "qoc_set_generator_ensemble": (C.c_int, [_vp, C.c_int, _dp, C.POINTER(_dp), _dp]),
+    "qoc_ensemble_size": (C.c_int, [_vp]),
+    "qoc_get_member_costs": (C.c_int, [_vp, _dp]),
+    "qoc_member_costs_dev": (_vp, [_vp]),
     "qoc_set_x0": (C.c_int, [_vp, _dp, C.c_int]),
     "qoc_set_cost": (C.c_int, [_vp, C.c_int, _dp, C.c_double]),
     "qoc_set_state_penalty": (C.c_int, [_vp, _ip, C.c_int, _ip, C.c_int, C.c_double]),

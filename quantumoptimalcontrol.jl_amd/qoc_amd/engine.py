@@ -115,6 +115,56 @@ class GrapeEngine:
         self._chk(self._lib.qoc_set_generators(self._h, _ptr(a0), arr))
         self._gen_key = key
 
+    def set_generator_ensemble(self, A0s, As, weights=None):
+        """Robust control (include/qoc.h qoc_set_generator_ensemble): every pulse is evaluated over the E generator
+        sets A0s (E, N, N) and As (nu arrays of (E, N, N), or (nu, E, N, N)), as systems.ensemble_members returns
+        them, and eval_device / eval_spline / minimize_spline_device / allgather_best then work on
+        J̄ = Σ_e weights[e] J(u; member e) and its gradient.  weights: E values used as given (None: 1/E each).
+        The members keep the block layout of the generators the engine was made with (the nominal set, which need
+        not be a member); propagate / grape_sensitivity and the other split calls raise QOCError
+        (QOC_ERR_UNSUPPORTED) until the ensemble is cleared.  set_generators clears it."""
+        A0s = np.asarray(A0s, dtype=np.complex128)
+        if A0s.ndim != 3 or A0s.shape[1:] != (self.N, self.N):
+            raise ValueError(f"A0s must be (E, N, N) with N={self.N}, got {A0s.shape}")
+        E = A0s.shape[0]
+        if len(As) != self.nu:
+            raise ValueError(f"expected {self.nu} stacks of control generators, got {len(As)}")
+        As = [np.asarray(a, dtype=np.complex128) for a in As]
+        for a in As:
+            if a.shape != A0s.shape:
+                raise ValueError(f"every stack of control generators must be {A0s.shape}, got {a.shape}")
+        a0 = np.concatenate([_cm_complex(a) for a in A0s]).view(np.float64)
+        aj = [np.concatenate([_cm_complex(x) for x in a]).view(np.float64) for a in As]
+        arr = (_dp * self.nu)(*[_ptr(a) for a in aj])
+        w = None
+        if weights is not None:
+            w = np.ascontiguousarray(weights, dtype=np.float64)
+            if w.shape != (E,):
+                raise ValueError(f"weights must have E={E} entries, got shape {w.shape}")
+        self._chk(self._lib.qoc_set_generator_ensemble(self._h, E, _ptr(a0), arr, _ptr(w) if w is not None else None))
+        self._gen_key = None  # so that a later set_generators reaches the library (and clears the ensemble) in any case
+
+    def clear_generator_ensemble(self):
+        """Back to the one generator set of set_generators; a plain eval is then bitwise what it was before."""
+        self._chk(self._lib.qoc_set_generator_ensemble(self._h, 0, None, None, None))
+
+    @property
+    def ensemble_size(self) -> int:
+        """Members of the generator ensemble, 0 when none is set."""
+        return int(self._lib.qoc_ensemble_size(self._h))
+
+    def member_costs(self) -> np.ndarray:
+        """J (B, E) of every (pulse, member) of the last ensemble eval, the state penalty included (synchronises):
+        the hook for worst-case objectives.  member_costs_device() is the same buffer's device pointer."""
+        E = self.ensemble_size
+        out = np.zeros((self.B, max(E, 1)))
+        self._chk(self._lib.qoc_get_member_costs(self._h, _ptr(out)))
+        return out
+
+    def member_costs_device(self) -> int:
+        """Device pointer of the B x E member costs (0 without an ensemble), valid while the ensemble is set."""
+        return int(self._lib.qoc_member_costs_dev(self._h) or 0)
+
     def set_x0(self, x0, per_seed: bool = False):
         x0 = np.asarray(x0, dtype=np.complex128)
         if per_seed:

@@ -198,6 +198,29 @@ class Problem:
         return len(self.A)
 
 
+def ensemble_members(prob, dA0=(), amp_scales=()):
+    """Generator sets for robust control (GrapeEngine.set_generator_ensemble): member e is A0 + dA0[e] with every
+    control generator times amp_scales[e].  dA0: Δt-prescaled perturbations of the drift, -i δH Δt (a detuning, a
+    coupling spread); amp_scales: drive-amplitude calibration factors.  Either may be empty (no perturbation / scale
+    1); when both are given they have one entry per member.  Returns the stacked (A0s (E, N, N), As: nu arrays of
+    (E, N, N)).  A member stays exactly skew-Hermitian when dA0[e] is (sums and real multiples keep A = -A^H entry by
+    entry) and inside prob's invariant blocks when dA0[e] couples no rows that prob's generators keep apart."""
+    dA0 = [np.asarray(d, dtype=np.complex128) for d in dA0]
+    amp = [float(a) for a in amp_scales]
+    if dA0 and amp and len(dA0) != len(amp):
+        raise ValueError(f"dA0 has {len(dA0)} members and amp_scales {len(amp)}")
+    E = max(len(dA0), len(amp))
+    if E < 1:
+        raise ValueError("an ensemble needs at least one member (dA0 or amp_scales)")
+    A0 = np.asarray(prob.A0, dtype=np.complex128)
+    for d in dA0:
+        if d.shape != A0.shape:
+            raise ValueError(f"every dA0 must be {A0.shape}, got {d.shape}")
+    A0s = np.stack([A0 + dA0[e] if dA0 else A0.copy() for e in range(E)])
+    As = [np.stack([np.asarray(a, dtype=np.complex128) * (amp[e] if amp else 1.0) for e in range(E)]) for a in prob.A]
+    return A0s, As
+
+
 # ---------------------------------------------------------------------------
 # BASELINE.json configurations
 # ---------------------------------------------------------------------------
