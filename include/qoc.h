@@ -112,7 +112,8 @@ int qoc_set_generators(qoc_ctx* ctx, const double* A0, const double* const* Aj);
  * Workspace (allocated by the setter, counted in info[3], freed on clear and qoc_destroy): the members' tables, and
  *   per (pulse, member) J, 2m λ_N coefficients and Nt x nu values of dJdu.
  * qoc_ensemble_size: E, 0 = none.  qoc_get_member_costs: J_{b,e} of the last ensemble eval (B x E, member fastest;
- *   synchronises; QOC_ERR_STATE without an ensemble or before its first eval): the hook for worst-case objectives.
+ *   synchronises; QOC_ERR_STATE without an ensemble or before its first eval), for post-processing; the worst-case
+ *   objectives themselves are qoc_set_ensemble_objective's.
  * qoc_member_costs_dev: the same buffer on the device (NULL without an ensemble), valid while this ensemble is set and
  *   written by every ensemble eval on qoc_stream. */
 int qoc_set_generator_ensemble(qoc_ctx* ctx, int E, const double* A0s, const double* const* Ajs,
@@ -120,6 +121,59 @@ int qoc_set_generator_ensemble(qoc_ctx* ctx, int E, const double* A0s, const dou
 int qoc_ensemble_size(qoc_ctx* ctx);
 int qoc_get_member_costs(qoc_ctx* ctx, double* Jm);
 double* qoc_member_costs_dev(qoc_ctx* ctx);
+/* The ensemble's objective: what qoc_eval_dev and everything built on it (qoc_eval_spline, qoc_minimize_spline_dev,
+ * the best-(J, seed) pick) minimise over the members.  Let w_e >= 0 be the ensemble's weights as given, W = Σ_e w_e
+ * (added in ascending e) and J_e the member costs of one pulse, the state penalty included.  Every objective is a
+ * value J̄ and per-pulse member weights ω_e >= 0 with Σ_e ω_e = W, and dJ̄/du = Σ_e ω_e dJ_e/du.  Members with w_e = 0
+ * never carry weight and never enter a maximum.
+ *   QOC_ENS_MEAN (default)   ω_e = w_e: the weighted mean, on the code path described above, bit for bit.
+ *   QOC_ENS_MAX              e* = argmax J_e over w_e > 0, the lowest e on ties; ω_{e*} = W, all others 0;
+ *                            J̄ = W J_{e*}.
+ *   QOC_ENS_CVAR, param = α in (0, 1]: the mean of the worst α-fraction.  Order the members by J descending, ties by
+ *                            ascending e; before_e = Σ w_f over the members ahead of e, added in ascending f;
+ *                            ω_e = min(w_e, max(0, α W - before_e)) / α; J̄ = Σ_e ω_e J_e.  α = 1 is the mean, an α no
+ *                            larger than the worst member's share the maximum.
+ *   QOC_ENS_LSE, param = β > 0, finite: a smooth maximum.  M = max J_e over w_e > 0, d_e = J_e - M,
+ *                            s = Σ_e (w_e / W) expm1(β d_e), J̄ = W (M + log1p(s) / β), ω_e = w_e e^{β d_e} / (1 + s)
+ *                            (the expm1 / log1p form: the plain log Σ exp loses ε / β to cancellation at small β).
+ * Sums: J̄ (MAX, CVaR), s and dJ̄/du are accumulated as acc = fma(ω_e, v_e, acc) from 0 in ascending e, without
+ *   atomics.  A member whose ω_e is exactly 0 is skipped, not multiplied by zero: its gradient row may be stale or
+ *   NaN.  If any J_e with w_e > 0 is not finite, every ω_e of that pulse is NaN; J̄ and the pulse's gradient are then
+ *   NaN and nothing is skipped.
+ * qoc_set_ensemble_objective: QOC_ERR_ARG for an unknown kind, an α outside (0, 1] or a β that is not finite and > 0
+ *   (param is ignored under MEAN and MAX).  A setting of the context, valid with or without an ensemble set; it
+ *   survives qoc_set_generator_ensemble (replace or clear) and qoc_set_generators.  Like the ensemble's setter it
+ *   materialises lazily kept states / co-states and invalidates the last forward; the last backward's record and the
+ *   best-(J, seed) pick stay.  A failed call (argument or allocation) changes nothing.
+ * Routes of an eval under a non-mean objective: 1 = the fused launch for every (pulse, member), the weights, the
+ *   ω-weighted sum; 2 = the forward half for every (pulse, member), the weights, the backward half only where ω is not
+ *   0, the ω-weighted sum.  LSE takes route 1.  MAX and CVaR take route 2 when n_act / E is at most a measured
+ *   threshold and the launch has enough workgroups per compute unit for the skipped ones to make room (both measured,
+ *   DESIGN.md §5), n_act = 1 + the largest k for which the k smallest positive weights sum to less than α W (MAX: 1):
+ *   decided from the objective, the weights and B E alone, never from data, when one of the two setters completes the
+ *   pair (ensemble + non-mean objective); QOC_ENS_SKIP=0|1 in the environment, read then, forces route 1 | 2.
+ *   Both routes give the same bits.  What is refused under an ensemble stays refused under every objective.
+ * qoc_get_ensemble_objective: the setting, and route = the form of the last ensemble eval (0 = none since a setter,
+ *   1 = fused, 2 = forward + active backward); any of the three pointers may be NULL.
+ * qoc_get_member_weights: ω of the last ensemble eval, B x E with the member index fastest (synchronises;
+ *   QOC_ERR_STATE without an ensemble or before its first eval since a setter); under MEAN w_e for every pulse.
+ *   qoc_member_weights_dev: the device buffer the evals under a non-mean objective write (NULL without an ensemble or
+ *   under MEAN, where there is no per-pulse buffer).
+ * qoc_member_grads_dev: the B E x Nt x nu member gradients dJ_{b,e}/du (row b E + e), for callers with objectives of
+ *   their own; NULL without an ensemble.  After an eval that took route 2, the rows of members whose ω was 0 hold
+ *   whatever an earlier eval left there (possibly nothing meaningful): read those rows only under route 1 or MEAN.
+ * Workspace: ω (B x E doubles) and, for route 2, G (with a penalty on blocks of 2 rows also D) at the segment ends per
+ *   (pulse, member); allocated by whichever of the two setters completes the pair, counted in info[3], freed with the
+ *   ensemble and at qoc_destroy. */
+#define QOC_ENS_MEAN 0
+#define QOC_ENS_MAX 1
+#define QOC_ENS_CVAR 2
+#define QOC_ENS_LSE 3
+int qoc_set_ensemble_objective(qoc_ctx* ctx, int kind, double param);
+int qoc_get_ensemble_objective(qoc_ctx* ctx, int* kind, double* param, int* route);
+int qoc_get_member_weights(qoc_ctx* ctx, double* om);
+double* qoc_member_weights_dev(qoc_ctx* ctx);
+double* qoc_member_grads_dev(qoc_ctx* ctx);
 /* x0 (N x m) shared by all seeds (per_seed = 0) or B x N x m (per_seed = 1) — propagate :14. */
 int qoc_set_x0(qoc_ctx* ctx, const double* x0, int per_seed);
 /* Terminal cost: kind QOC_COST_TRACE (X_target N x m, normalisation n),

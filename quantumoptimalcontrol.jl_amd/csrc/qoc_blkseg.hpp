@@ -109,6 +109,9 @@ struct BlksegParams {
   // rad[3] | mur[3] | mui[3] in place of the ones above
   int E;
   const double* ens;
+  // the member-aware backward half (BLKSEG_BWD with ENS): ω[B][E] of k_ens_weights; workgroup v returns at once when
+  // omega[v] == 0 and leaves its row of dJdu as it was (nullptr: every workgroup runs)
+  const double* omega;
 };
 enum { BLKSEG_FUSED = 0, BLKSEG_FWD = 1, BLKSEG_BWD = 2 };
 
@@ -920,20 +923,25 @@ __device__ __forceinline__ double seg_uniform(double x) {
 // Built-in costs only (TRACE / ZCAL), no co-state source, unpacked states, skew-Hermitian generators
 // (the host's blkseg_ok).  PEN: with the state penalty on the rows P and columns C of sp.prow / sp.pcol (the header
 // comment's penalty section); PEN = false is the unpenalised kernel, instruction for instruction.
-// ENS (BLKSEG_FUSED only): one workgroup per (pulse, member of a generator ensemble), blockIdx.x = v = pulse * E +
-// member.  The pulse selects the row of u (and of a per-seed x_0), the member its generator table and nine scalars
+// ENS: one workgroup per (pulse, member of a generator ensemble), blockIdx.x = v = pulse * E + member.  The pulse selects the row of u (and of a per-seed x_0), the member its generator table and nine scalars
 // (uniform loads in the prologue); every output (J, the coefficients, dJdu) is indexed by v and goes to the ensemble's
 // workspace, u_copy is written by member 0's workgroups alone, and the second copies and the best-pair epilogue are
-// off.  Phases 1-3 are the same code; ENS = false is the kernel without any of it.
+// off.  Phases 1-3 are the same code; ENS = false is the kernel without any of it.  The halves under ENS (the risk
+// objectives' route 2, qoc_run_blkseg_ens.hip): BLKSEG_FWD writes J, the coefficients, G and D indexed by v;
+// BLKSEG_BWD of a workgroup whose member weight sp.omega[v] is exactly 0 returns before it reads anything else.
 template <int NB, int ORD, int WMAX, int MODE = BLKSEG_FUSED, bool PEN = false, bool ENS = false>
 __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, const BlkArgs bk, const BlksegParams sp_) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
-  static_assert(!ENS || MODE == BLKSEG_FUSED, "the ensemble launch is the fused eval");
+  static_assert(!ENS || MODE != BLKSEG_FWD || ORD == 1, "the forward half has one instantiation");
+  static_assert(!ENS || MODE == BLKSEG_FUSED || !(PEN && NB == 3), "penalised blocks of 3 rows have no ensemble eval");
   // the launch's parameters: the kernel argument itself, or (ENS) a copy with the member's table and scalars
   BlksegParams spm;
   int ens_p = blockIdx.x;
   if constexpr (ENS) {
     const int v = blockIdx.x, Ee = sp_.E;
+    if constexpr (MODE == BLKSEG_BWD) {  // a member without weight in this pulse's objective: nothing to compute
+      if (sp_.omega && sp_.omega[v] == 0.0) return;
+    }
     ens_p = v / Ee;
     const int e = v - ens_p * Ee;
     spm = sp_;
@@ -2016,6 +2024,153 @@ __global__ __launch_bounds__(256) void k_ens_reduce(int B, int E, int n, const d
     for (int e = 0; e < E; ++e) acc = fma(w[e], Jm[(size_t)idx * E + e], acc);
     J[idx] = acc;
     if (J2) J2[idx] = acc;
+  }
+}
+
+// The risk objectives over an ensemble (include/qoc.h qoc_set_ensemble_objective): from the member costs Jm[B][E] of
+// a launch and the weights w[E], the member weights ω[B][E] (Σ_e ω_e = W = Σ_e w_e) and J̄ into J and J2.
+//   QOC_ENS_MAX   e* = argmax over w_e > 0 (lowest e on ties), ω_{e*} = W, J̄ = W J_{e*}
+//   QOC_ENS_CVAR  before_e = Σ w_f over the f ahead of e (J_f > J_e, or equal and f < e), in ascending f;
+//                 ω_e = min(w_e, max(0, α W - before_e)) / α, J̄ = Σ_e ω_e J_e
+//   QOC_ENS_LSE   M = max over w_e > 0, d_e = J_e - M, s = Σ_e (w_e / W) expm1(β d_e), J̄ = W (M + log1p(s) / β),
+//                 ω_e = w_e exp(β d_e) / (1 + s)
+// One wave per pulse (blockIdx.x), lane l owns members l, l + 64, ...; costs and weights are staged in LDS when they
+// fit (LDS: 3 E doubles of dynamic LDS), otherwise read where they are, with the pulse's row of om as the scratch of
+// the LSE terms: E is not capped.  Ranks are found by counting over all E costs (O(E^2 / 64) per wave).  Every sum
+// over the members (W, s, before_e, J̄) is a serial loop in ascending member order (fma from 0 for s and J̄; zero ω
+// skipped in J̄), so the result does not depend on the grid.  A non-finite cost among the members with w_e > 0 makes
+// every ω of the pulse and J̄ NaN.
+enum { ENS_OBJ_MEAN = 0, ENS_OBJ_MAX = 1, ENS_OBJ_CVAR = 2, ENS_OBJ_LSE = 3 };  // (= QOC_ENS_*)
+template <bool LDS>
+__global__ __launch_bounds__(64) void k_ens_weights(int E, int kind, double param, const double* __restrict__ w,
+                                                    const double* __restrict__ Jm, double* __restrict__ om,
+                                                    double* __restrict__ J, double* __restrict__ J2) {
+  extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+  const int p = blockIdx.x, l = threadIdx.x;
+  const double* Jp = Jm + (size_t)p * E;
+  const double* wp = w;
+  double* const op = om + (size_t)p * E;
+  double* T = op;  // the LSE terms, then ω again for the J̄ sum
+  if constexpr (LDS) {
+    double* const sJ = reinterpret_cast<double*>(smem);
+    double* const sw = sJ + E;
+    for (int e = l; e < E; e += 64) {
+      sJ[e] = Jp[e];
+      sw[e] = w[e];
+    }
+    Jp = sJ;
+    wp = sw;
+    T = sw + E;
+    __syncthreads();
+  }
+  // W in ascending order (every lane the same loop), the maximum with its lowest index, the non-finite flag
+  double Wt = 0.0;
+  for (int e = 0; e < E; ++e) Wt += wp[e];
+  double M = -__builtin_inf();
+  int im = 0x7fffffff, bad = 0;
+  for (int e = l; e < E; e += 64) {
+    if (!(wp[e] > 0.0)) continue;
+    const double v = Jp[e];
+    if (!isfinite(v)) bad = 1;
+    if (v > M || im == 0x7fffffff) {  // (ascending e per lane: a tie keeps the lower index)
+      M = v;
+      im = e;
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    const double oM = __shfl_xor(M, off);
+    const int oi = __shfl_xor(im, off);
+    bad |= __shfl_xor(bad, off);
+    if (oi != 0x7fffffff && (im == 0x7fffffff || oM > M || (oM == M && oi < im))) {
+      M = oM;
+      im = oi;
+    }
+  }
+  if (bad) {
+    const double qn = __builtin_nan("");
+    for (int e = l; e < E; e += 64) op[e] = qn;
+    if (l == 0) {
+      J[p] = qn;
+      if (J2) J2[p] = qn;
+    }
+    return;
+  }
+  double s = 0.0;
+  if (kind == ENS_OBJ_LSE) {
+    for (int e = l; e < E; e += 64) T[e] = wp[e] > 0.0 ? expm1(param * (Jp[e] - M)) : 0.0;
+    __syncthreads();
+    for (int e = 0; e < E; ++e)
+      if (wp[e] > 0.0) s = fma(wp[e] / Wt, T[e], s);
+    __syncthreads();
+  }
+  const double aW = param * Wt;
+  for (int e = l; e < E; e += 64) {
+    const double we = wp[e], Je = Jp[e];
+    double o;
+    if (kind == ENS_OBJ_MAX) {
+      o = e == im ? Wt : 0.0;
+    } else if (kind == ENS_OBJ_CVAR) {
+      double before = 0.0;
+      for (int f = 0; f < E; ++f) {
+        const double Jf = Jp[f];
+        if (Jf > Je || (Jf == Je && f < e)) before += wp[f];
+      }
+      o = fmin(we, fmax(0.0, aW - before)) / param;
+    } else {
+      o = we > 0.0 ? we * exp(param * (Je - M)) / (1.0 + s) : 0.0;
+    }
+    op[e] = o;
+    if constexpr (LDS) T[e] = o;
+  }
+  __syncthreads();  // (ω of the other lanes: LDS, or the pulse's own row of om in global memory)
+  if (l == 0) {
+    double Jb;
+    if (kind == ENS_OBJ_LSE) {
+      Jb = Wt * (M + log1p(s) / param);
+    } else {
+      Jb = 0.0;
+      for (int e = 0; e < E; ++e) {
+        const double o = T[e];
+        if (o != 0.0) Jb = fma(o, Jp[e], Jb);
+      }
+    }
+    J[p] = Jb;
+    if (J2) J2[p] = Jb;
+  }
+}
+
+// k_ens_reduce with per-pulse weights ω[B][E] (k_ens_weights): dJdu[p][i] = Σ_e ω_pe g[p E + e][i] in ascending e as
+// acc = fma(ω_pe, v_e, acc) from 0.  A member whose ω is exactly 0 is skipped, not multiplied: its row may be stale or
+// NaN (the member-aware backward leaves it alone), and a worst-case reduction reads one row per pulse, not E.  A NaN ω
+// is not skipped.  J̄ is k_ens_weights' and is not touched here.
+template <bool VEC>
+__global__ __launch_bounds__(256) void k_ens_reduce_w(int B, int E, int n, const double* __restrict__ om,
+                                                      const double* __restrict__ g, double* __restrict__ dJdu) {
+  const int nv = VEC ? n / 2 : n;
+  const long long idx = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+  if (idx >= (long long)B * nv) return;
+  const int p = (int)(idx / nv), i = (int)(idx - (long long)p * nv);
+  const double* const op = om + (size_t)p * E;
+  if constexpr (VEC) {
+    const double2* src = reinterpret_cast<const double2*>(g + (size_t)p * E * n) + i;
+    double2 acc = make_double2(0.0, 0.0);
+    for (int e = 0; e < E; ++e) {
+      const double oe = op[e];
+      if (oe == 0.0) continue;
+      const double2 v = src[(size_t)e * nv];
+      acc.x = fma(oe, v.x, acc.x);
+      acc.y = fma(oe, v.y, acc.y);
+    }
+    reinterpret_cast<double2*>(dJdu + (size_t)p * n)[i] = acc;
+  } else {
+    const double* src = g + (size_t)p * E * n + i;
+    double acc = 0.0;
+    for (int e = 0; e < E; ++e) {
+      const double oe = op[e];
+      if (oe == 0.0) continue;
+      acc = fma(oe, src[(size_t)e * n], acc);
+    }
+    dJdu[(size_t)p * n + i] = acc;
   }
 }
 

@@ -460,16 +460,19 @@ static int ens_eval_check(qoc_ctx* c, int order) {
 }
 // drops the ensemble and its workspace (the stream is drained first: a queued eval may still read them)
 static void ens_clear(qoc_ctx* c) {
-  if (!c->ens_E && !c->ens_bytes) return;
+  if (!c->ens_E && !c->ens_bytes && !c->ens_risk_bytes) return;
   if (c->stream) hipStreamSynchronize(c->stream);
   for (void* p : {(void*)c->d_ens_gtab, (void*)c->d_ens_prm, (void*)c->d_ens_w, (void*)c->d_ens_J, (void*)c->d_ens_coef,
-                  (void*)c->d_ens_g})
+                  (void*)c->d_ens_g, (void*)c->d_ens_om, (void*)c->d_ens_gseg})
     if (p) hipFree(p);
   c->d_ens_gtab = nullptr;
-  c->d_ens_prm = c->d_ens_w = c->d_ens_J = c->d_ens_g = nullptr;
+  c->d_ens_prm = c->d_ens_w = c->d_ens_J = c->d_ens_g = c->d_ens_om = nullptr;
   c->d_ens_coef = nullptr;
-  c->dev_bytes -= c->ens_bytes;
-  c->ens_bytes = 0;
+  c->d_ens_gseg = nullptr;
+  c->dev_bytes -= c->ens_bytes + c->ens_risk_bytes;
+  c->ens_bytes = c->ens_risk_bytes = c->ens_gseg_bytes = 0;
+  c->ens_last_route = 0;
+  c->h_ens_w.clear();
   c->ens_E = 0;
   c->ens_costs = false;
 }
@@ -882,24 +885,29 @@ int qoc_set_generator_ensemble(qoc_ctx* c, int E, const double* A0s, const doubl
   if (int r0 = blk_materialize(c)) return r0;
   // the new ensemble's buffers first, so that a failed allocation leaves the context as it was
   const size_t BE = (size_t)c->B * E;
-  const size_t bytes[6] = {tabs.size() * sizeof(double), prm.size() * sizeof(double), (size_t)E * sizeof(double),
+  // (a non-mean objective set earlier: this setter completes the pair and allocates its workspace too)
+  const EnsPlan pl = blkseg_ens_plan(c, E, w.data(), c->ens_obj, c->ens_obj_param);
+  const size_t bytes[8] = {tabs.size() * sizeof(double), prm.size() * sizeof(double), (size_t)E * sizeof(double),
                            BE * sizeof(double), BE * 2 * c->m_user * sizeof(cx<double>),
-                           BE * c->Nt * c->nu * sizeof(double)};
-  void* buf[6] = {};
+                           BE * c->Nt * c->nu * sizeof(double), pl.om_bytes, pl.gseg_bytes};
+  void* buf[8] = {};
   size_t total = 0;
-  for (int i = 0; i < 6; ++i) {
+  for (int i = 0; i < 8; ++i) {
+    if (!bytes[i]) continue;
     const hipError_t e_ = hipMalloc(&buf[i], bytes[i]);
     if (e_ != hipSuccess) {
-      for (int q = 0; q < i; ++q) hipFree(buf[q]);
+      for (int q = 0; q < i; ++q)
+        if (buf[q]) hipFree(buf[q]);
       return fail(c, QOC_ERR_HIP, "the ensemble's workspace (%zu bytes): %s", bytes[i], hipGetErrorString(e_));
     }
-    total += bytes[i];
+    if (i < 6) total += bytes[i];
   }
   hipError_t e_ = hipMemcpy(buf[0], tabs.data(), bytes[0], hipMemcpyHostToDevice);
   if (e_ == hipSuccess) e_ = hipMemcpy(buf[1], prm.data(), bytes[1], hipMemcpyHostToDevice);
   if (e_ == hipSuccess) e_ = hipMemcpy(buf[2], w.data(), bytes[2], hipMemcpyHostToDevice);
   if (e_ != hipSuccess) {
-    for (void* p : buf) hipFree(p);
+    for (void* p : buf)
+      if (p) hipFree(p);
     return fail(c, QOC_ERR_HIP, "the ensemble's tables: %s", hipGetErrorString(e_));
   }
   ens_clear(c);
@@ -909,8 +917,14 @@ int qoc_set_generator_ensemble(qoc_ctx* c, int E, const double* A0s, const doubl
   c->d_ens_J = (double*)buf[3];
   c->d_ens_coef = (cx<double>*)buf[4];
   c->d_ens_g = (double*)buf[5];
+  c->d_ens_om = (double*)buf[6];
+  c->d_ens_gseg = (double2*)buf[7];
+  c->ens_gseg_bytes = pl.gseg_bytes;
+  c->ens_risk_bytes = pl.om_bytes + pl.gseg_bytes;
+  c->ens_route = pl.route;
+  c->h_ens_w = w;
   c->ens_bytes = total;
-  c->dev_bytes += total;
+  c->dev_bytes += total + c->ens_risk_bytes;
   c->ens_E = E;
   c->fwd.valid = false;  // states are per member from here on
   return QOC_OK;
@@ -926,6 +940,90 @@ int qoc_get_member_costs(qoc_ctx* c, double* Jm) {
   if (!c->ens_costs) return fail(c, QOC_ERR_STATE, "no eval since the ensemble was set");
   HIPCHK(c, hipSetDevice(c->dev));
   HIPCHK(c, hipMemcpyAsync(Jm, c->d_ens_J, (size_t)c->B * c->ens_E * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  return QOC_OK;
+}
+
+int qoc_set_ensemble_objective(qoc_ctx* c, int kind, double param) {
+  if (!c) return fail(nullptr, QOC_ERR_ARG, "null context");
+  if (kind != QOC_ENS_MEAN && kind != QOC_ENS_MAX && kind != QOC_ENS_CVAR && kind != QOC_ENS_LSE)
+    return fail(c, QOC_ERR_ARG, "unknown ensemble objective %d", kind);
+  if (kind == QOC_ENS_CVAR && !(param > 0.0 && param <= 1.0))
+    return fail(c, QOC_ERR_ARG, "QOC_ENS_CVAR needs alpha in (0, 1] (got %g)", param);
+  if (kind == QOC_ENS_LSE && !(std::isfinite(param) && param > 0.0))
+    return fail(c, QOC_ERR_ARG, "QOC_ENS_LSE needs a finite beta > 0 (got %g)", param);
+  if (kind == QOC_ENS_MEAN || kind == QOC_ENS_MAX) param = 0.0;
+  HIPCHK(c, hipSetDevice(c->dev));
+  // lazily kept states / co-states are rebuilt with the context as it is (as in qoc_set_generator_ensemble)
+  if (int r0 = blk_materialize(c)) return r0;
+  int route = 1;
+  if (c->ens_E) {
+    // with an ensemble set this setter completes the pair: ω, and G (D) at the segment ends where route 2 is taken;
+    // the new buffers first, so that a failed allocation leaves the context as it was
+    const EnsPlan pl = blkseg_ens_plan(c, c->ens_E, c->h_ens_w.data(), kind, param);
+    void *om = nullptr, *gs = nullptr;
+    if (pl.om_bytes && !c->d_ens_om) {
+      const hipError_t e_ = hipMalloc(&om, pl.om_bytes);
+      if (e_ != hipSuccess)
+        return fail(c, QOC_ERR_HIP, "the objective's workspace (%zu bytes): %s", pl.om_bytes, hipGetErrorString(e_));
+    }
+    if (pl.gseg_bytes > c->ens_gseg_bytes) {
+      const hipError_t e_ = hipMalloc(&gs, pl.gseg_bytes);
+      if (e_ != hipSuccess) {
+        if (om) hipFree(om);
+        return fail(c, QOC_ERR_HIP, "the objective's workspace (%zu bytes): %s", pl.gseg_bytes, hipGetErrorString(e_));
+      }
+    }
+    if (om) {
+      c->d_ens_om = (double*)om;
+      c->ens_risk_bytes += pl.om_bytes;
+      c->dev_bytes += pl.om_bytes;
+    }
+    if (gs) {
+      if (c->d_ens_gseg) {
+        if (c->stream) hipStreamSynchronize(c->stream);  // a queued eval may still read it
+        hipFree(c->d_ens_gseg);
+      }
+      c->d_ens_gseg = (double2*)gs;
+      c->ens_risk_bytes += pl.gseg_bytes - c->ens_gseg_bytes;
+      c->dev_bytes += pl.gseg_bytes - c->ens_gseg_bytes;
+      c->ens_gseg_bytes = pl.gseg_bytes;
+    }
+    route = pl.route;
+  }
+  c->ens_obj = kind;
+  c->ens_obj_param = param;
+  c->ens_route = route;
+  c->ens_last_route = 0;  // the weights of the last eval belong to the old objective
+  c->fwd.valid = false;
+  return QOC_OK;
+}
+
+int qoc_get_ensemble_objective(qoc_ctx* c, int* kind, double* param, int* route) {
+  if (!c) return fail(nullptr, QOC_ERR_ARG, "null context");
+  if (kind) *kind = c->ens_obj;
+  if (param) *param = c->ens_obj_param;
+  if (route) *route = c->ens_E ? c->ens_last_route : 0;
+  return QOC_OK;
+}
+
+double* qoc_member_weights_dev(qoc_ctx* c) {
+  return c && c->ens_E && c->ens_obj != QOC_ENS_MEAN ? c->d_ens_om : nullptr;
+}
+
+double* qoc_member_grads_dev(qoc_ctx* c) { return c && c->ens_E ? c->d_ens_g : nullptr; }
+
+int qoc_get_member_weights(qoc_ctx* c, double* om) {
+  if (!c || !om) return fail(c, QOC_ERR_ARG, "null argument");
+  if (!c->ens_E) return fail(c, QOC_ERR_STATE, "no generator ensemble is set");
+  if (!c->ens_last_route) return fail(c, QOC_ERR_STATE, "no eval since the ensemble or its objective was set");
+  HIPCHK(c, hipSetDevice(c->dev));
+  if (c->ens_obj == QOC_ENS_MEAN) {  // ω_e = w_e for every pulse
+    HIPCHK(c, hipStreamSynchronize(c->stream));
+    for (int b = 0; b < c->B; ++b) std::copy(c->h_ens_w.begin(), c->h_ens_w.end(), om + (size_t)b * c->ens_E);
+    return QOC_OK;
+  }
+  HIPCHK(c, hipMemcpyAsync(om, c->d_ens_om, (size_t)c->B * c->ens_E * sizeof(double), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));
   return QOC_OK;
 }

@@ -12,6 +12,7 @@
 //   qoc_run_blkp.hip      blocks of 5..16 rows on stored / interpolating propagators
 //   qoc_run_blku.hip      blocks of <= 4 rows on block propagators
 //   qoc_run_blkseg.hip    the segmented block eval (blocks of <= 3 rows: one launch for J and dJdu)
+//   qoc_run_blkseg_ens.hip  its halves per (pulse, member) of a generator ensemble, the risk objectives' weights
 // Each kernel template is launched from one translation unit only; the context (qoc_ctx) and the entry points
 // between the units are declared here.
 #pragma once
@@ -273,6 +274,21 @@ struct qoc_ctx {
   double* d_ens_g = nullptr;         // B x E x Nt x nu member gradients
   size_t ens_bytes = 0;
   bool ens_costs = false;            // d_ens_J holds an eval's costs
+  // The ensemble's objective (qoc_set_ensemble_objective): a setting of the context that outlives the ensemble.
+  // Under a non-mean objective an ensemble eval forms per-pulse member weights ω (k_ens_weights) and takes one of two
+  // routes: 1 = the fused launch for every (pulse, member), 2 = the forward half for all, the backward half where ω
+  // is not 0.  ens_route is derived by blkseg_ens_plan from the objective, the weights and QOC_ENS_SKIP whenever one of
+  // the two setters completes the pair (ensemble + non-mean objective); that setter also allocates ω and, for route 2,
+  // G (and D) at the segment ends per (pulse, member).  Counted in dev_bytes (ens_risk_bytes), freed with the ensemble.
+  int ens_obj = 0;                   // QOC_ENS_MEAN / _MAX / _CVAR / _LSE
+  double ens_obj_param = 0.0;        // α (CVaR) or β (LSE), else 0
+  int ens_route = 1;                 // the route the next eval under a non-mean objective takes
+  int ens_last_route = 0;            // the last ensemble eval's: 0 = none since a setter, 1 = fused, 2 = forward + active backward
+  std::vector<double> h_ens_w;       // the weights, host copy
+  double* d_ens_om = nullptr;        // B x E member weights ω of the last eval under a non-mean objective
+  double2* d_ens_gseg = nullptr;     // B E x NB^2 x S x nblk complex G at the segment ends, and D behind it when penalised
+  size_t ens_gseg_bytes = 0, ens_risk_bytes = 0;
+  bool seg_attr_ens_half[2][5][2][2] = {};  // [NB - 2][order slot][forward, backward][penalised]: seg_attr for the ENS halves
   int* h_flag = nullptr;             // host-mapped stale-u flag of the queued check (k_compare_u_flags)
   int flag_turn = 0;                 // which of the two device flags d_flag[0 / 1] the next queued check writes
   hipEvent_t flag_ev = nullptr;      // recorded after that copy
@@ -532,6 +548,14 @@ int blkseg_eval(qoc_ctx* c, int order, const double* d_u, double* d_J, double* d
 // form of blocks of 3 rows); the eval itself: B E workgroups, then k_ens_reduce into d_J / the caller's J and d_dJdu
 bool blkseg_ens_ok(const qoc_ctx* c, int order);
 int blkseg_eval_ens(qoc_ctx* c, int order, const double* d_u, double* d_J, double* d_dJdu);
+// What an ensemble of E members with weights w needs under the objective (kind, param): the route of its evals (from
+// the objective, the weights and QOC_ENS_SKIP alone) and the bytes of ω and of G (and D) at the segment ends; zeros
+// under the mean.  Nothing on the context changes.
+struct EnsPlan {
+  int route = 1;
+  size_t om_bytes = 0, gseg_bytes = 0;
+};
+EnsPlan blkseg_ens_plan(qoc_ctx* c, int E, const double* w, int kind, double param);
 // the reference's split call form on the segmented eval: propagate = phases 0-2 (G at the segment ends to HBM),
 // grape_sensitivity = phase 3 (stale: the device flag of a stale-u check queued before it, or nullptr)
 bool blkseg_split_ok(const qoc_ctx* c);

@@ -2,9 +2,7 @@
 // the fused eval and of its forward and backward halves.
 #include <cstring>
 
-#include "qoc_blk_host.hpp"
-#include "qoc_blkseg.hpp"
-#include "qoc_internal.hpp"
+#include "qoc_blkseg_host.hpp"
 
 namespace qoc_host {
 
@@ -86,21 +84,6 @@ bool blkseg_ok(const qoc_ctx* c, int order) {
   if (env_is("QOC_BLKSEG", "0")) return false;
   if (c->mu != 0.0 && (env_is("QOC_BLKSEG_PEN", "0") || c->m > 32)) return false;  // (the column mask has 32 bits)
   return blkseg_shape(c).lds <= BLKSEG_LDS_MAX;
-}
-
-// (the exact tag has its own dispatch: blk_order_dispatch and BLK_ORDMAX stay the Taylor orders' alone, so the
-// k_blku_*, k_blkp_* and dense kernels keep refusing or routing QOC_DUKDP_EXACT as before)
-template <typename F>
-static hipError_t blkseg_dispatch(int NB, int order, F&& f) {
-  if (order == QOC_DUKDP_EXACT) {
-    const std::integral_constant<int, 0> ex;
-    if (NB == 2) return f(std::integral_constant<int, 2>(), ex);
-    return f(std::integral_constant<int, 3>(), ex);
-  }
-  return blk_order_dispatch(order, [&](auto ORD_) {
-    if (NB == 2) return f(std::integral_constant<int, 2>(), ORD_);
-    return f(std::integral_constant<int, 3>(), ORD_);
-  });
 }
 
 static int ensure_lazy_bufs(qoc_ctx* c) {
@@ -274,15 +257,90 @@ bool blkseg_ens_ok(const qoc_ctx* c, int order) {
   return !(blkseg_pen(c) && c->blk_nb == 3);  // (G and D per seed through HBM: not part of the ensemble eval)
 }
 
-// One eval of every pulse over the ensemble: the fused kernel on B E (pulse, member) workgroups writes the members'
-// J, coefficients and dJdu into the ensemble's workspace (and u into d_u, by member 0's workgroups, when the caller's
-// buffer is another one), then k_ens_reduce forms the weighted sums in d_J (and the caller's J) and d_dJdu.  Nothing
-// lazy is kept and the best-pair epilogue is off: k_argmin_seed picks from d_J.
+// When a MAX or CVaR eval takes route 2 (the forward half for every (pulse, member), the backward half where ω is not
+// 0) instead of the fused launch, from the sweeps of tools/bench_ensemble_risk.py on an MI355X ("Ensemble
+// evals"): at most ENS_SKIP_TAU of the members can carry weight, and the launch has at least ENS_SKIP_WG_PER_CU
+// workgroups per compute unit.  With fewer the skipped workgroups free compute units that have nothing else to do,
+// and the second launch and the round trip of G through HBM cost 3-12 %; at E = 8 one active member of 8 wins every
+// repeat from 4 workgroups per CU on (1.05-1.44 x), two of 8 lose on the cavity at 4 per CU.  QOC_ENS_SKIP=0|1
+// forces a route.
+constexpr double ENS_SKIP_TAU = 0.125;
+constexpr long long ENS_SKIP_WG_PER_CU = 4;
+
+EnsPlan blkseg_ens_plan(qoc_ctx* c, int E, const double* w, int kind, double param) {
+  EnsPlan pl;
+  if (E < 1 || kind == QOC_ENS_MEAN) return pl;
+  pl.om_bytes = (size_t)c->B * E * sizeof(double);
+  if (kind == QOC_ENS_MAX || kind == QOC_ENS_CVAR) {
+    // n_act: the most members that can carry weight whatever the costs: 1 + the largest k for which the k smallest
+    // positive weights sum to less than α W (the worst case puts the lightest members first)
+    int n_act = 1;
+    if (kind == QOC_ENS_CVAR) {
+      double W = 0.0;
+      std::vector<double> pos;
+      for (int e = 0; e < E; ++e) {
+        W += w[e];
+        if (w[e] > 0.0) pos.push_back(w[e]);
+      }
+      std::sort(pos.begin(), pos.end());
+      const double aW = param * W;
+      double acc = 0.0;
+      int k = 0;
+      for (double x : pos) {
+        acc += x;
+        if (!(acc < aW)) break;
+        ++k;
+      }
+      n_act = std::min(1 + k, (int)pos.size());
+    }
+    const bool filled = (long long)c->B * E >= ENS_SKIP_WG_PER_CU * std::max(1, c->ncu);
+    pl.route = filled && (double)n_act / E <= ENS_SKIP_TAU ? 2 : 1;
+    if (env_is("QOC_ENS_SKIP", "0")) pl.route = 1;
+    if (env_is("QOC_ENS_SKIP", "1")) pl.route = 2;
+  }
+  if (pl.route == 2) {  // G at every segment's end per (pulse, member), and D behind it when the eval is penalised
+    const int E_ctx = c->ens_E;
+    c->ens_E = E;  // (the launch shape counts B E workgroups)
+    const BlksegShape s = blkseg_shape(c);
+    c->ens_E = E_ctx;
+    pl.gseg_bytes = (blkseg_pen(c) ? 2 : 1) * (size_t)c->B * E * s.S * c->nblk * c->blk_nb * c->blk_nb * sizeof(double2);
+  }
+  return pl;
+}
+
+// One eval of every pulse over the ensemble.  Under the mean: the fused kernel on B E (pulse, member) workgroups writes
+// the members' J, coefficients and dJdu into the ensemble's workspace (and u into d_u, by member 0's workgroups, when
+// the caller's buffer is another one), then k_ens_reduce forms the weighted sums in d_J (and the caller's J) and
+// d_dJdu.  Under another objective (qoc_set_ensemble_objective) k_ens_weights forms the per-pulse member weights ω and
+// J̄ from the member costs and k_ens_reduce_w the ω-weighted gradient; route 1 has the fused launch in front of them,
+// route 2 the forward half for every workgroup, k_ens_weights, then the backward half, which returns at once where
+// ω is 0.  Nothing lazy is kept and the best-pair epilogue is off: k_argmin_seed picks from d_J.
 int blkseg_eval_ens(qoc_ctx* c, int order, const double* d_u, double* d_J, double* d_dJdu) {
   const BlksegShape s = blkseg_shape(c);
   BlksegParams sp;
   int r = blkseg_params(c, s, sp);
   if (r) return r;
+  const int kind = c->ens_obj;
+  const int route = kind == QOC_ENS_MEAN ? 1 : c->ens_route;
+  const size_t gcount = (size_t)c->B * c->ens_E * s.S * c->nblk * c->blk_nb * c->blk_nb;
+  if (kind != QOC_ENS_MEAN && !c->d_ens_om)
+    return fail(c, QOC_ERR_STATE, "the ensemble objective's workspace is missing");
+  if (route == 2) {
+    // (the setters sized G for the shape and the penalty of their time; a penalty set since may need D behind it)
+    const size_t gbytes = (blkseg_pen(c) ? 2 : 1) * gcount * sizeof(double2);
+    if (c->ens_gseg_bytes < gbytes) {
+      double2* q = nullptr;
+      HIPCHK(c, hipMalloc((void**)&q, gbytes));
+      if (c->d_ens_gseg) {
+        HIPCHK(c, hipStreamSynchronize(c->stream));
+        HIPCHK(c, hipFree(c->d_ens_gseg));
+      }
+      c->dev_bytes += gbytes - c->ens_gseg_bytes;
+      c->ens_risk_bytes += gbytes - c->ens_gseg_bytes;
+      c->d_ens_gseg = q;
+      c->ens_gseg_bytes = gbytes;
+    }
+  }
   sp.u = d_u;
   sp.u_copy = d_u != c->d_u ? c->d_u : nullptr;
   sp.dJdu = c->d_ens_g;
@@ -293,24 +351,42 @@ int blkseg_eval_ens(qoc_ctx* c, int order, const double* d_u, double* d_J, doubl
   sp.ens = c->d_ens_prm;
   c->jbest.direct = false;
   const int mk = mark_begin(c, 2);
-  hipError_t e = blkseg_launch_ens(c, order, s, sp);
-  if (e == hipSuccess) {
-    const int n = c->Nt * c->nu;
-    const bool vec = c->nu == 2 && (reinterpret_cast<size_t>(d_dJdu) & 15) == 0;
-    const long long thr = std::max<long long>((long long)c->B * (vec ? n / 2 : n), c->B);
-    const unsigned grid = (unsigned)((thr + 255) / 256);
-    double* const J2 = d_J && d_J != c->d_J ? d_J : nullptr;
-    if (vec)
-      hipLaunchKernelGGL(k_ens_reduce<true>, dim3(grid), dim3(256), 0, c->stream, c->B, c->ens_E, n, c->d_ens_w,
-                         c->d_ens_g, c->d_ens_J, d_dJdu, c->d_J, J2);
-    else
-      hipLaunchKernelGGL(k_ens_reduce<false>, dim3(grid), dim3(256), 0, c->stream, c->B, c->ens_E, n, c->d_ens_w,
-                         c->d_ens_g, c->d_ens_J, d_dJdu, c->d_J, J2);
-    e = hipGetLastError();
+  hipError_t e;
+  if (route == 2) {
+    sp.gseg = c->d_ens_gseg;
+    sp.dseg = c->d_ens_gseg + gcount;
+    e = blkseg_launch_ens_half(c, BLKSEG_FWD, 1, s, sp);
+    if (e == hipSuccess) e = ens_weights_launch(c, d_J);
+    if (e == hipSuccess) {
+      sp.u_copy = nullptr;  // (written by the forward half)
+      sp.omega = c->d_ens_om;
+      e = blkseg_launch_ens_half(c, BLKSEG_BWD, order, s, sp);
+    }
+    if (e == hipSuccess) e = ens_reduce_w_launch(c, d_dJdu);
+  } else {
+    e = blkseg_launch_ens(c, order, s, sp);
+    if (e == hipSuccess && kind != QOC_ENS_MEAN) {
+      e = ens_weights_launch(c, d_J);
+      if (e == hipSuccess) e = ens_reduce_w_launch(c, d_dJdu);
+    } else if (e == hipSuccess) {
+      const int n = c->Nt * c->nu;
+      const bool vec = c->nu == 2 && (reinterpret_cast<size_t>(d_dJdu) & 15) == 0;
+      const long long thr = std::max<long long>((long long)c->B * (vec ? n / 2 : n), c->B);
+      const unsigned grid = (unsigned)((thr + 255) / 256);
+      double* const J2 = d_J && d_J != c->d_J ? d_J : nullptr;
+      if (vec)
+        hipLaunchKernelGGL(k_ens_reduce<true>, dim3(grid), dim3(256), 0, c->stream, c->B, c->ens_E, n, c->d_ens_w,
+                           c->d_ens_g, c->d_ens_J, d_dJdu, c->d_J, J2);
+      else
+        hipLaunchKernelGGL(k_ens_reduce<false>, dim3(grid), dim3(256), 0, c->stream, c->B, c->ens_E, n, c->d_ens_w,
+                           c->d_ens_g, c->d_ens_J, d_dJdu, c->d_J, J2);
+      e = hipGetLastError();
+    }
   }
   mark_end(c, mk);
   if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "k_blkseg_eval (ensemble) launch: %s", hipGetErrorString(e));
   c->ens_costs = true;
+  c->ens_last_route = route;
   return QOC_OK;
 }
 

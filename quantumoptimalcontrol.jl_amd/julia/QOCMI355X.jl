@@ -153,6 +153,30 @@ function member_costs(c::MI355XCache)
     return Jm
 end
 
+"""
+    set_ensemble_objective!(cache, kind, param=0.0)
+
+What the ensemble evals minimise over the members (include/qoc.h `qoc_set_ensemble_objective`): `kind` one of `:mean`
+(default, J̄ = Σ_e w_e J_e), `:max` (the worst member), `:cvar` with `param` = α in (0, 1] (the mean of the worst
+α-fraction) or `:lse` with `param` = β > 0 (the smooth maximum).  A setting of the context: it holds with or without an
+ensemble and survives `set_generator_ensemble!` and `upload!`.  Not run, like the shim's other ensemble calls.
+"""
+function set_ensemble_objective!(c::MI355XCache, kind::Symbol, param::Real=0.0)
+    k = findfirst(==(kind), (:mean, :max, :cvar, :lse))
+    k === nothing && error("kind must be :mean, :max, :cvar or :lse, got $kind")
+    check(ccall((:qoc_set_ensemble_objective, libqoc), Cint, (Ptr{Cvoid}, Cint, Cdouble), c.ctx, k - 1, Float64(param)),
+          c.ctx)
+    return nothing
+end
+
+"""The member weights ω of the cache's one pulse at the last ensemble eval (`qoc_get_member_weights`; Σ ω = Σ w, and
+dJ̄/du = Σ_e ω_e dJ_e/du); not run, see above."""
+function member_weights(c::MI355XCache)
+    om = zeros(max(ensemble_size(c), 1))
+    check(ccall((:qoc_get_member_weights, libqoc), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), c.ctx, om), c.ctx)
+    return om
+end
+
 """States of the last propagate, fetched lazily (the reference returns cache.x, Nt+1 matrices)."""
 struct LazyStates <: AbstractVector{Matrix{ComplexF64}}
     c::MI355XCache

@@ -6,7 +6,7 @@ olof3/QuantumOptimalControl.jl) runs in hand-written HIP kernels for gfx950 in
 ``libqoc_mi355x.so`` (C ABI: include/qoc.h).  This package is the host mirror of the
 reference's interface for that path; it has no CPU fallback.
 """
-from . import systems  # noqa: F401
+from . import robust, systems  # noqa: F401
 from ._lib import QOCError, StaleCacheError  # noqa: F401
 from .api import (  # noqa: F401
     MI355XCache,

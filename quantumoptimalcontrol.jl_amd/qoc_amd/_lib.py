@@ -24,6 +24,7 @@ QOC_DUKDP_EXACT = 0
 QOC_COST_TRACE = 0
 QOC_COST_ZCAL = 1
 QOC_COST_EXTERNAL = 2
+QOC_ENS_MEAN, QOC_ENS_MAX, QOC_ENS_CVAR, QOC_ENS_LSE = 0, 1, 2, 3
 QOC_PROP_EXPM = 0
 QOC_PROP_TSIT5 = 1
 QOC_ENV = {"tunable_bus": 0, "drag": 1, "sinebasis": 2}
@@ -57,6 +58,11 @@ SIGNATURES = {
     "qoc_ensemble_size": (C.c_int, [_vp]),
     "qoc_get_member_costs": (C.c_int, [_vp, _dp]),
     "qoc_member_costs_dev": (_vp, [_vp]),
+    "qoc_set_ensemble_objective": (C.c_int, [_vp, C.c_int, C.c_double]),
+    "qoc_get_ensemble_objective": (C.c_int, [_vp, _ip, _dp, _ip]),
+    "qoc_get_member_weights": (C.c_int, [_vp, _dp]),
+    "qoc_member_weights_dev": (_vp, [_vp]),
+    "qoc_member_grads_dev": (_vp, [_vp]),
     "qoc_set_x0": (C.c_int, [_vp, _dp, C.c_int]),
     "qoc_set_cost": (C.c_int, [_vp, C.c_int, _dp, C.c_double]),
     "qoc_set_state_penalty": (C.c_int, [_vp, _ip, C.c_int, _ip, C.c_int, C.c_double]),

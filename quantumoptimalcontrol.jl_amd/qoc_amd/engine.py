@@ -165,6 +165,51 @@ class GrapeEngine:
         """Device pointer of the B x E member costs (0 without an ensemble), valid while the ensemble is set."""
         return int(self._lib.qoc_member_costs_dev(self._h) or 0)
 
+    _ENS_KINDS = ("mean", "max", "cvar", "lse")
+
+    def set_ensemble_objective(self, kind: str, param=None):
+        """What the ensemble evals minimise over the members (include/qoc.h qoc_set_ensemble_objective; the formulas
+        are qoc_amd.robust's): "mean" (default) J̄ = Σ_e w_e J_e; "max" the worst member, W J_{e*}; "cvar" with
+        param = α in (0, 1], the mean of the worst α-fraction; "lse" with param = β > 0, the smooth maximum
+        W (M + log1p(Σ_e (w_e / W) expm1(β (J_e - M))) / β).  Every objective has per-pulse member weights ω_e >= 0
+        with Σ_e ω_e = W = Σ_e w_e and dJ̄/du = Σ_e ω_e dJ_e/du; members with ω_e = 0 are skipped.  A setting of the
+        engine: it holds with or without an ensemble set and survives set_generator_ensemble, its clearing and
+        set_generators.  eval_device, eval_spline, minimize_spline_device and allgather_best follow it."""
+        if kind not in self._ENS_KINDS:
+            raise ValueError(f"kind must be one of {self._ENS_KINDS}, got {kind!r}")
+        if kind in ("cvar", "lse") and param is None:
+            raise ValueError(f"{kind} needs its parameter")
+        self._chk(self._lib.qoc_set_ensemble_objective(self._h, self._ENS_KINDS.index(kind),
+                                                       0.0 if param is None else float(param)))
+
+    @property
+    def ensemble_objective(self):
+        """(kind, param, route): the objective as set (param None under "mean" and "max") and the form of the last
+        ensemble eval: 0 = none since a setter, 1 = the fused launch for every (pulse, member), 2 = the forward half
+        for all and the backward half only for members with weight."""
+        k, p, r = C.c_int(0), C.c_double(0.0), C.c_int(0)
+        self._chk(self._lib.qoc_get_ensemble_objective(self._h, C.byref(k), C.byref(p), C.byref(r)))
+        kind = self._ENS_KINDS[k.value]
+        return kind, (p.value if kind in ("cvar", "lse") else None), r.value
+
+    def member_weights(self) -> np.ndarray:
+        """ω (B, E) of the last ensemble eval (synchronises): the weights w for every pulse under "mean"."""
+        E = self.ensemble_size
+        out = np.zeros((self.B, max(E, 1)))
+        self._chk(self._lib.qoc_get_member_weights(self._h, _ptr(out)))
+        return out
+
+    def member_weights_device(self) -> int:
+        """Device pointer of the B x E member weights the evals under a non-mean objective write (0 without an
+        ensemble or under "mean")."""
+        return int(self._lib.qoc_member_weights_dev(self._h) or 0)
+
+    def member_grads_device(self) -> int:
+        """Device pointer of the B E x Nt x nu member gradients (row b E + e; 0 without an ensemble), for objectives
+        of the caller's own.  After an eval on route 2 the rows of members with ω = 0 hold whatever an earlier eval
+        left there."""
+        return int(self._lib.qoc_member_grads_dev(self._h) or 0)
+
     def set_x0(self, x0, per_seed: bool = False):
         x0 = np.asarray(x0, dtype=np.complex128)
         if per_seed:
