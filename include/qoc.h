@@ -174,6 +174,44 @@ int qoc_get_ensemble_objective(qoc_ctx* ctx, int* kind, double* param, int* rout
 int qoc_get_member_weights(qoc_ctx* ctx, double* om);
 double* qoc_member_weights_dev(qoc_ctx* ctx);
 double* qoc_member_grads_dev(qoc_ctx* ctx);
+/* Gate duration as a variable: a per-seed time scale, a setting of the context.  With it set, seed b evolves under
+ * tau_b (A0 + Σ_j u_jk A_j) in every slice: its gate duration is tau_b times the nominal one, and seeds of different
+ * durations share one launch (a gate-time sweep is one batch).
+ * qoc_eval_dev then returns J_b and dJ_b/du_b at fixed tau_b and leaves dJ_b/dtau_b at fixed u_b in the context's
+ *   buffer.  J includes the state penalty, which stays Σ_{k=0}^{Nt} L(x_k), not rescaled by tau.  J and dJdu are what
+ *   the engine returns for generators scaled by tau_b (orders 1-4: the reference's truncated formula on the scaled
+ *   generators).  dJ/dtau = Σ_k Re<lambda_{k+1}, A_k x_{k+1}> with the full co-state (the penalty's sources included)
+ *   is the exact derivative of the computed J at every dUkdp_order: exp(tau A_k) commutes with A_k, no series enters.
+ *   Everything built on qoc_eval_dev follows with no change of its own: qoc_eval_spline[_dev],
+ *   qoc_minimize_spline_dev, and the best (J, seed) of qoc_allgather_best[_dev] / qoc_set_best_output.
+ * qoc_set_time_scale: copies B host values; every value must be finite and > 0 (QOC_ERR_ARG otherwise, context
+ *   unchanged); NULL clears.  QOC_ERR_UNSUPPORTED on a QOC_FP32 context and while a generator ensemble is set
+ *   (qoc_set_generator_ensemble is refused likewise while a time scale is set; both leave the earlier setting in place).
+ *   Allocates 2 B doubles on first use, counted in info[3], freed on clear and at qoc_destroy.  Like the ensemble's
+ *   setter it materialises lazily kept states / co-states and invalidates the last forward.  The setting survives
+ *   qoc_set_generators, qoc_set_x0 and qoc_set_cost.  tau = 1 for every seed is not special-cased: it runs the same
+ *   kernels and gives the plain eval's J and dJdu.  After clearing, a plain eval is bitwise what it was before.
+ * qoc_time_scale_dev: the context's B values on the device (NULL when none set).  The caller may overwrite them on
+ *   qoc_stream between evals (an optimiser of its own, say); every eval reads them at launch.  Values written that
+ *   way are not checked: a non-finite or non-positive tau_b gives unspecified results, possibly NaN, for that seed only.
+ * qoc_get_time_scale_grad: dJ_b/dtau_b of the last eval under the time scale, B host values (synchronises;
+ *   QOC_ERR_STATE without a time scale or before its first eval since the setter).  qoc_time_scale_grad_dev: the same
+ *   buffer on the device (NULL when none set), written by every such eval on qoc_stream.  The sum is formed in a fixed
+ *   order without atomics: a seed's dJ/dtau has the same bits alone and inside any batch of the same launch shape.
+ * Supported where the segmented eval applies: invariant blocks of 2 or 3 rows, exactly skew-Hermitian generators,
+ *   QOC_FP64, QOC_COST_TRACE and QOC_COST_ZCAL, orders 1-4 and QOC_DUKDP_EXACT, the state penalty on blocks of 2 rows
+ *   in one launch and on blocks of 3 rows as a forward and a backward launch.
+ * QOC_ERR_UNSUPPORTED, leaving the context and the caller's output buffers as they were: an eval that kernel does not
+ *   take (a co-state source, qoc_set_compression, generators without blocks of 2-3 rows, QOC_BLKSEG=0,
+ *   QOC_CONCURRENT=0, Tsit5; QOC_COST_EXTERNAL gives its usual QOC_ERR_STATE); and, while a time scale is set,
+ *   qoc_propagate[_dev], qoc_grape_sensitivity[_dev], qoc_propagate_spline, qoc_sensitivity_spline,
+ *   qoc_propagate_envelope and qoc_eval_envelope[_dev].
+ * What it leaves: an eval under a time scale keeps no states and nothing lazy (qoc_get_states: QOC_ERR_STATE); the
+ *   co-states of the last plain backward stay readable, and qoc_get_info keeps reporting the last plain backward's route. */
+int qoc_set_time_scale(qoc_ctx* ctx, const double* tau);
+double* qoc_time_scale_dev(qoc_ctx* ctx);
+int qoc_get_time_scale_grad(qoc_ctx* ctx, double* dJdtau);
+double* qoc_time_scale_grad_dev(qoc_ctx* ctx);
 /* x0 (N x m) shared by all seeds (per_seed = 0) or B x N x m (per_seed = 1) — propagate :14. */
 int qoc_set_x0(qoc_ctx* ctx, const double* x0, int per_seed);
 /* Terminal cost: kind QOC_COST_TRACE (X_target N x m, normalisation n),

@@ -112,6 +112,10 @@ struct BlksegParams {
   // the member-aware backward half (BLKSEG_BWD with ENS): ω[B][E] of k_ens_weights; workgroup v returns at once when
   // omega[v] == 0 and leaves its row of dJdu as it was (nullptr: every workgroup runs)
   const double* omega;
+  // the per-seed time scale (the TS instantiations; nullptr otherwise): seed b runs on tau[b] times the generators
+  // (the table and the nine scalars above, scaled in the prologue) and leaves dJ/dτ_b at fixed u in dJdtau[b]
+  const double* tau;
+  double* dJdtau;
 };
 enum { BLKSEG_FUSED = 0, BLKSEG_FWD = 1, BLKSEG_BWD = 2 };
 
@@ -918,6 +922,18 @@ __device__ __forceinline__ double seg_uniform(double x) {
   return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
 }
 
+// a value computed alike in every lane (a product of uniform values, say), moved to scalar registers: through an
+// opaque vector register, because the compiler drops the readfirstlane of a value it knows to be uniform and then
+// keeps the result in vector registers
+__device__ __forceinline__ double seg_scalar(double x) {
+  const long long b = __double_as_longlong(x);
+  int lo = (int)(b & 0xffffffffll), hi = (int)(b >> 32);
+  asm volatile("" : "+v"(lo), "+v"(hi));
+  lo = __builtin_amdgcn_readfirstlane(lo);
+  hi = __builtin_amdgcn_readfirstlane(hi);
+  return __longlong_as_double(((long long)hi << 32) | (unsigned int)lo);
+}
+
 // One workgroup per seed (blockIdx.x), W = blockDim / 64 waves, UPW segments of nblk lanes per wave (lanes past
 // UPW nblk idle).  ORD: the gradient's order 1..4, or 0 for the exact one (the header comment's phase 3).
 // Built-in costs only (TRACE / ZCAL), no co-state source, unpacked states, skew-Hermitian generators
@@ -929,13 +945,35 @@ __device__ __forceinline__ double seg_uniform(double x) {
 // off.  Phases 1-3 are the same code; ENS = false is the kernel without any of it.  The halves under ENS (the risk
 // objectives' route 2, qoc_run_blkseg_ens.hip): BLKSEG_FWD writes J, the coefficients, G and D indexed by v;
 // BLKSEG_BWD of a workgroup whose member weight sp.omega[v] is exactly 0 returns before it reads anything else.
-template <int NB, int ORD, int WMAX, int MODE = BLKSEG_FUSED, bool PEN = false, bool ENS = false>
+// TS: the gate duration as a per-seed variable.  Seed b runs on τ_b (A_0 + Σ_j u_jk A_j), τ_b = sp.tau[b]: the
+// prologue multiplies the nine scalars and every table entry on its way to LDS by τ_b, so that ρ, J, P, the series
+// class, e^{μ_k}, z and the exact term count follow from the seed's own scaled values and phases 1-3 run as they are
+// (seeds of any durations share a launch); θ_cap is not scaled.  With U_k = exp(τ A_k) and [A_k, U_k] = 0,
+//   dJ/dτ = Σ_k Re⟨λ_{k+1}, A_k x_{k+1}⟩ = Σ_k Σ_blocks Re tr(A_k G_{k+1}) = Σ_k Σ_blocks Re tr(A_k K_k U_k):
+// phase 3 adds Re tr(X_k K_k U_k) per lane and slice, X_k = τ A_k as the loop holds it (unshifted, un-halved) and
+// K_k U_k = G_k before its own penalty source; the phase-free loops carry z̄ G, so they add the complex trace and z
+// is applied once per lane.  One fixed-order reduction over lanes and waves follows (no atomics), and
+// dJdtau[b] = sum / τ_b: the exact derivative of the computed J at every ORD.  BLKSEG_FWD with TS only scales.
+template <int NB, int ORD, int WMAX, int MODE = BLKSEG_FUSED, bool PEN = false, bool ENS = false, bool TS = false>
 __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, const BlkArgs bk, const BlksegParams sp_) {
   extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
   static_assert(!ENS || MODE != BLKSEG_FWD || ORD == 1, "the forward half has one instantiation");
   static_assert(!ENS || MODE == BLKSEG_FUSED || !(PEN && NB == 3), "penalised blocks of 3 rows have no ensemble eval");
-  // the launch's parameters: the kernel argument itself, or (ENS) a copy with the member's table and scalars
+  static_assert(!(ENS && TS), "a time scale and a generator ensemble do not combine");
+  // the launch's parameters: the kernel argument itself, or a copy with (ENS) the member's table and scalars or (TS)
+  // the seed's scaled scalars
   BlksegParams spm;
+  double tau = 1.0;
+  if constexpr (TS) {
+    tau = seg_uniform(sp_.tau[blockIdx.x]);
+    spm = sp_;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) {  // (the products are vector results: back to scalar registers, where the plain kernel has them)
+      spm.rad[j] = seg_scalar(sp_.rad[j] * tau);
+      spm.mur[j] = seg_scalar(sp_.mur[j] * tau);
+      spm.mui[j] = seg_scalar(sp_.mui[j] * tau);
+    }
+  }
   int ens_p = blockIdx.x;
   if constexpr (ENS) {
     const int v = blockIdx.x, Ee = sp_.E;
@@ -959,7 +997,7 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
     spm.coef2 = nullptr;
     spm.done = nullptr;
   }
-  const BlksegParams& sp = ENS ? spm : sp_;
+  const BlksegParams& sp = ENS || TS ? spm : sp_;
   const int bp = ENS ? ens_p : (int)blockIdx.x;  // the pulse: the row of u, of its copy and of a per-seed x_0
   if constexpr (MODE == BLKSEG_BWD) {  // a stale u (the check queued before this launch): leave every output alone
     if (sp.stale && *sp.stale != 0) return;
@@ -1030,8 +1068,16 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
 #pragma unroll
   for (int i = 0; i < NB; ++i) brw[i] = bk.brow[beta * NB + i];
   {
+    if constexpr (TS) {  // the scaled blocks: nothing downstream sees an unscaled entry
+      if (tid < ntab) gsh[tid] = make_double2(tab0.x * tau, tab0.y * tau);
+      for (int q = tid + nthr; q < ntab; q += nthr) {
+        const double2 v = sp.gtab[q];
+        gsh[q] = make_double2(v.x * tau, v.y * tau);
+      }
+    } else {
     if (tid < ntab) gsh[tid] = tab0;
     for (int q = tid + nthr; q < ntab; q += nthr) gsh[q] = sp.gtab[q];
+    }
     if constexpr (MODE != BLKSEG_BWD) {
       double2* const xN2 = reinterpret_cast<double2*>(xN);
       if (hasx) {
@@ -1814,6 +1860,9 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
     sk2_pauli2(Sk2{gk[1].d0 + mu1i, gk[1].d1 + mu1i, gk[1].r, gk[1].q}, pa1);
     sk2_pauli2(Sk2{gk[2].d0 + mu2i, gk[2].d1 + mu2i, gk[2].r, gk[2].q}, pa2);
   }
+  // TS: the lane's Σ_k tr(X_k K_k U_k) over its slices (the imaginary part in the phase-free loops only, where the
+  // trace is of z̄ G and z turns it back at the end)
+  double tsr = 0.0, tsi = 0.0;
   // upre: the slice's controls where the caller has read them already (the no-select loop's read-ahead)
   auto p3_fast = [&](int jj, auto SEL_, auto K_, auto ZD_, const double2* upre = nullptr) {
     constexpr bool SEL = decltype(SEL_)::value;
@@ -1853,6 +1902,16 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
       // (ZD: μ_k = i Im μ_0, the same value)
       const double mki = ZD ? sp.mui[0] : fma(u.y, mu2i, fma(u.x, mu1i, sp.mui[0]));
       const Sk2 x{ah.d0 + mki, ah.d1 + mki, ah.r, ah.q};
+      if constexpr (TS) {
+        // tr(X_k K_k U_k) on the skew X = [[i d0, r + i q], [-r + i q, i d1]]; t = K_k U_k (ZD: z̄ times it).  Lanes
+        // without a segment are dropped at the reduction.
+        const double t_re = fma(-x.d0, ti[0], fma(-x.d1, ti[3], fma(x.r, tr[2] - tr[1], -x.q * (ti[2] + ti[1]))));
+        tsr += !SEL || act ? t_re : 0.0;
+        if constexpr (ZD) {
+          const double t_im = fma(x.d0, tr[0], fma(x.d1, tr[3], fma(x.r, ti[2] - ti[1], x.q * (tr[2] + tr[1]))));
+          tsi += !SEL || act ? t_im : 0.0;
+        }
+      }
       double acc1, acc2;
       if constexpr (ORD == 0) {
         sk2_contract_exact<ZD>(x, pa1, pa2, Kr, Ki, ex, acc1, acc2, zx3);
@@ -1912,6 +1971,29 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
         // G_{k+1} takes the source of λ_{k+1}, 2 μ D_{k+1} Π; then D_k = U_k^H D_{k+1} U_k
         if (pm && act) pen_step(ur[0], ui[0]);
       }
+      // TS: the slice's Re tr(X_k G), in one of two places (the same sum: X_k commutes with U_k).  Blocks of 3 rows at
+      // order 1, whose contraction needs no X: here, as Re tr(X_k G_{k+1}) with the source of λ_{k+1} in G and
+      // X_k = 2^J Â + μ_k I from the formation's Â, still in registers and dead afterwards (forming X for the trace
+      // alone took these kernels from 158 to 256 VGPRs).  Everything else: below, on the X the contraction forms (the
+      // early form there keeps Â live across the two products and spills).
+      constexpr bool TSE = TS && NB == 3 && ORD == 1;
+      if constexpr (TSE) {
+        double t_re = 0.0, gtr = 0.0, gti = 0.0;
+#pragma unroll
+        for (int i = 0; i < NB; ++i) {
+          gtr += Gr[i * NB + i];
+          gti += Gi[i * NB + i];
+#pragma unroll
+          for (int q = 0; q < NB; ++q)
+            t_re = fma(ar[0][i * NB + q], Gr[q * NB + i], fma(-ai[0][i * NB + q], Gi[q * NB + i], t_re));
+        }
+        const double2 sv = *reinterpret_cast<const double2*>(rk[0] + 2);
+        const double v1 = ldexp(sv.x, J), v2 = ldexp(sv.y, J);
+        const double nr = fma(v2, sp.mur[2], fma(v1, sp.mur[1], sp.mur[0]));
+        const double ni = fma(v2, sp.mui[2], fma(v1, sp.mui[1], sp.mui[0]));
+        t_re = fma(nr, gtr, fma(-ni, gti, ldexp(t_re, J)));
+        tsr += act ? t_re : 0.0;
+      }
       // K_k = U_k^H G_{k+1}, G_k = K_k U_k
       double Kr[E], Ki[E], tr[E], ti[E];
       seg_mm<NB, true, false>(ur[0], ui[0], Gr, Gi, Kr, Ki);
@@ -1943,6 +2025,26 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
           xr[e] = fma(u2, g2.x, fma(u1, g1.x, g0.x)) + (e % (NB + 1) == 0 ? dgr : 0.0);
           xi[e] = fma(u2, g2.y, fma(u1, g1.y, g0.y)) + (e % (NB + 1) == 0 ? dgi : 0.0);
         }
+      }
+      if constexpr (TS && !TSE) {
+        // Re tr(X_k G_k), G_k = K_k U_k just formed (before its own source); the exact series' X is the shifted one,
+        // so μ_k tr G_k is added apart.  Taken before G goes to its LDS row (GST) and the contraction needs the registers.
+        double t_re = 0.0;
+#pragma unroll
+        for (int i = 0; i < NB; ++i)
+#pragma unroll
+          for (int q = 0; q < NB; ++q)
+            t_re = fma(xr[i * NB + q], Gr[q * NB + i], fma(-xi[i * NB + q], Gi[q * NB + i], t_re));
+        if constexpr (ORD == 0) {
+          double gtr = 0.0, gti = 0.0;
+#pragma unroll
+          for (int i = 0; i < NB; ++i) {
+            gtr += Gr[i * NB + i];
+            gti += Gi[i * NB + i];
+          }
+          t_re = fma(mkr, gtr, fma(-mki, gti, t_re));
+        }
+        tsr += act ? t_re : 0.0;
       }
       double acc1, acc2;
       // The exact series on blocks of 3 rows keeps X, L and R live over its loop; with G beside them the kernel spills.
@@ -1978,7 +2080,22 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
   BK_T(t4);
   BK_ADD(3, t4 - t3);
   SEGW_SET(16 + w, t4 - t0);
+  if constexpr (TS) {
+    // the lanes' sums: z on the phase-free loops' complex trace, a butterfly over the wave (the same order in every
+    // launch), then the waves in order below, behind the barrier
+    double v = su ? zr * tsr - zi * tsi : tsr;
+    v = sact ? v : 0.0;
+    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off);
+    if (l == 0) red[w] = v;
+  }
   __syncthreads();
+  if constexpr (TS) {
+    if (tid == 0) {
+      double sum = 0.0;
+      for (int q = 0; q < W; ++q) sum += red[q];
+      sp.dJdtau[b] = sum / tau;
+    }
+  }
   double* const og = sp.dJdu + (size_t)b * Nt * nu;
   for (int i = tid; i < Nt * nu; i += nthr) og[i] = dJ[i];
   if (MODE == BLKSEG_FUSED && sp.terms && tid == 0)
@@ -2175,3 +2292,4 @@ __global__ __launch_bounds__(256) void k_ens_reduce_w(int B, int E, int n, const
 }
 
 }  // namespace qoc
+

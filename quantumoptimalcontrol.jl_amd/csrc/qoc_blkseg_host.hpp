@@ -1,5 +1,6 @@
 // qoc_blkseg_host.hpp — what the translation units that launch the segmented eval share (qoc_run_blkseg.hip: the
-// plain and the fused ensemble launches; qoc_run_blkseg_ens.hip: the ensemble's forward and backward halves).
+// plain and the fused ensemble launches; qoc_run_blkseg_ens.hip: the ensemble's forward and backward halves;
+// qoc_run_blkseg_ts.hip: the launches under a time scale).
 #pragma once
 #include "qoc_blk_host.hpp"
 #include "qoc_blkseg.hpp"
@@ -26,6 +27,10 @@ static hipError_t blkseg_dispatch(int NB, int order, F&& f) {
 // ignores the order).  sp is complete (the member tables, E, gseg / dseg, and for the backward half omega); J and the
 // coefficients go to the ensemble's workspace.
 hipError_t blkseg_launch_ens_half(qoc_ctx* c, int mode, int order, const BlksegShape& s, const BlksegParams& sp);
+
+// The segmented eval under a per-seed time scale on B workgroups (qoc_run_blkseg_ts.hip; mode BLKSEG_FUSED, or
+// BLKSEG_FWD / BLKSEG_BWD for penalised blocks of 3 rows).  sp is complete, with tau and dJdtau.
+hipError_t blkseg_launch_ts(qoc_ctx* c, int mode, int order, const BlksegShape& s, const BlksegParams& sp);
 
 // ω and J̄ from the member costs of the launch before it (k_ens_weights), and the ω-weighted sum of the member
 // gradients (k_ens_reduce_w), on the context's stream

@@ -458,6 +458,33 @@ static int ens_eval_check(qoc_ctx* c, int order) {
                 "ZCAL, no co-state source, no packing, the state penalty on blocks of 2 rows)");
   return QOC_OK;
 }
+// With a time scale set (qoc_set_time_scale) only qoc_eval_dev and what is built on it run: the other paths know
+// nothing of τ.
+static int ts_barred(qoc_ctx* c, const char* what) {
+  return fail(c, QOC_ERR_UNSUPPORTED,
+              "%s is not available while a time scale is set (qoc_set_time_scale); qoc_eval_dev and its callers are",
+              what);
+}
+// what qoc_eval_dev refuses under a time scale, before anything on the context changes
+static int ts_eval_check(qoc_ctx* c, int order) {
+  if (!c->ts_on) return QOC_OK;
+  if (order < 0 || order > 4) return fail(c, QOC_ERR_ARG, "dUkdp_order must be 1..4 or QOC_DUKDP_EXACT (got %d)", order);
+  if (!c->concurrent || !blkseg_ts_ok(c, order))
+    return fail(c, QOC_ERR_UNSUPPORTED,
+                "the time scale (qoc_set_time_scale) runs on the segmented eval only (blocks of 2-3 rows, exactly "
+                "skew-Hermitian generators, fp64, TRACE / ZCAL, the matrix exponential, no co-state source, no packing)");
+  return QOC_OK;
+}
+// drops the time scale and its buffer (the stream is drained first: a queued eval may still read it)
+static void ts_clear(qoc_ctx* c) {
+  if (c->d_ts) {
+    if (c->stream) hipStreamSynchronize(c->stream);
+    hipFree(c->d_ts);
+    c->d_ts = nullptr;
+    c->dev_bytes -= (size_t)2 * c->B * sizeof(double);
+  }
+  c->ts_on = c->ts_grad = false;
+}
 // drops the ensemble and its workspace (the stream is drained first: a queued eval may still read them)
 static void ens_clear(qoc_ctx* c) {
   if (!c->ens_E && !c->ens_bytes && !c->ens_risk_bytes) return;
@@ -639,6 +666,7 @@ void qoc_destroy(qoc_ctx* c) {
   if (c->d_gc_part) hipFree(c->d_gc_part);
   if (c->d_gseg) hipFree(c->d_gseg);
   ens_clear(c);
+  ts_clear(c);
   if (c->d_blkp_ctab) hipFree(c->d_blkp_ctab);
   if (c->d_blkp_M) hipFree(c->d_blkp_M);
   if (c->d_blkp_ph) hipFree(c->d_blkp_ph);
@@ -833,6 +861,9 @@ int qoc_set_generator_ensemble(qoc_ctx* c, int E, const double* A0s, const doubl
     c->fwd.valid = false;
     return QOC_OK;
   }
+  if (c->ts_on)
+    return fail(c, QOC_ERR_UNSUPPORTED,
+                "qoc_set_generator_ensemble: not while a time scale is set (qoc_set_time_scale); clear it first");
   if (!c->have_gen) return fail(c, QOC_ERR_STATE, "generators not set (qoc_set_generators comes first)");
   if (!A0s || !Ajs) return fail(c, QOC_ERR_ARG, "null argument");
   for (int j = 0; j < c->nu; ++j)
@@ -927,6 +958,54 @@ int qoc_set_generator_ensemble(qoc_ctx* c, int E, const double* A0s, const doubl
   c->dev_bytes += total + c->ens_risk_bytes;
   c->ens_E = E;
   c->fwd.valid = false;  // states are per member from here on
+  return QOC_OK;
+}
+
+int qoc_set_time_scale(qoc_ctx* c, const double* tau) {
+  if (!c) return fail(nullptr, QOC_ERR_ARG, "null context");
+  HIPCHK(c, hipSetDevice(c->dev));
+  if (!tau) {
+    if (!c->ts_on && !c->d_ts) return QOC_OK;
+    ts_clear(c);
+    c->fwd.valid = false;
+    return QOC_OK;
+  }
+  if (c->prec != QOC_FP64)
+    return fail(c, QOC_ERR_UNSUPPORTED, "qoc_set_time_scale: the time scale is fp64 only (QOC_FP32 context)");
+  if (c->ens_E)
+    return fail(c, QOC_ERR_UNSUPPORTED,
+                "qoc_set_time_scale: not while a generator ensemble is set (qoc_set_generator_ensemble); clear it first");
+  for (int b = 0; b < c->B; ++b)
+    if (!std::isfinite(tau[b]) || !(tau[b] > 0.0))
+      return fail(c, QOC_ERR_ARG, "tau[%d] = %g: the time scale must be finite and > 0", b, tau[b]);
+  // lazily kept states / co-states are rebuilt with the context as it is (an eval under the scale keeps nothing lazy)
+  if (int r0 = blk_materialize(c)) return r0;
+  const size_t bytes = (size_t)2 * c->B * sizeof(double);
+  if (!c->d_ts) {
+    HIPCHK(c, hipMalloc((void**)&c->d_ts, bytes));
+    c->dev_bytes += bytes;
+  }
+  // on the context's stream, behind every queued eval that still reads the earlier values
+  HIPCHK(c, hipMemcpyAsync(c->d_ts, tau, bytes / 2, hipMemcpyHostToDevice, c->stream));
+  HIPCHK(c, hipMemsetAsync(c->d_ts + c->B, 0, bytes / 2, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  c->ts_on = true;
+  c->ts_grad = false;
+  c->fwd.valid = false;  // the states of the last propagate are not this scale's
+  return QOC_OK;
+}
+
+double* qoc_time_scale_dev(qoc_ctx* c) { return c && c->ts_on ? c->d_ts : nullptr; }
+
+double* qoc_time_scale_grad_dev(qoc_ctx* c) { return c && c->ts_on ? c->d_ts + c->B : nullptr; }
+
+int qoc_get_time_scale_grad(qoc_ctx* c, double* dJdtau) {
+  if (!c || !dJdtau) return fail(c, QOC_ERR_ARG, "null argument");
+  if (!c->ts_on) return fail(c, QOC_ERR_STATE, "no time scale is set (qoc_set_time_scale)");
+  if (!c->ts_grad) return fail(c, QOC_ERR_STATE, "no eval since the time scale was set");
+  HIPCHK(c, hipSetDevice(c->dev));
+  HIPCHK(c, hipMemcpyAsync(dJdtau, c->d_ts + c->B, (size_t)c->B * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
   return QOC_OK;
 }
 
@@ -1223,6 +1302,7 @@ int qoc_set_compression(qoc_ctx* c, const int* rows1, int nr1, const int* cols1,
 
 int qoc_propagate_dev(qoc_ctx* c, const double* d_u, double* d_J) {
   if (c && c->ens_E) return ens_barred(c, "qoc_propagate_dev");
+  if (c && c->ts_on) return ts_barred(c, "qoc_propagate_dev");
   int r = check_ready(c);
   if (r) return r;
   if (!d_u) return fail(c, QOC_ERR_ARG, "d_u is null");
@@ -1232,6 +1312,7 @@ int qoc_propagate_dev(qoc_ctx* c, const double* d_u, double* d_J) {
 
 int qoc_grape_sensitivity_dev(qoc_ctx* c, const double* d_u, int order, double* d_dJdu) {
   if (c && c->ens_E) return ens_barred(c, "qoc_grape_sensitivity_dev");
+  if (c && c->ts_on) return ts_barred(c, "qoc_grape_sensitivity_dev");
   int r = check_ready(c);
   if (r) return r;
   if (!c->fwd.valid) return fail(c, QOC_ERR_STATE, "grape_sensitivity called before propagate");
@@ -1274,6 +1355,17 @@ int qoc_eval_dev(qoc_ctx* c, const double* d_u, int order, double* d_J, double* 
     c->h_coef.clear();
     return QOC_OK;
   }
+  if (c->ts_on) {
+    // a per-seed time scale: the segmented eval's TS instantiations, dJ/dτ beside J and dJdu.  No states are kept (the
+    // rebuild chains know nothing of τ): the forward stays invalid and the last backward's record stands.
+    if ((r = ts_eval_check(c, order))) return r;
+    forward_begin(c);
+    if ((r = blkseg_eval_ts(c, order, d_u, d_J, out))) return r;
+    c->props_since_reset++;
+    c->h_u.clear();
+    c->h_coef.clear();
+    return QOC_OK;
+  }
   if (c->concurrent && blkseg_ok(c, order)) {
     // block propagators with the time axis in segments: one launch reads u (and copies it to d_u) and writes J and
     // dJdu; x_k and λ_k are rebuilt on demand (qoc_blkseg.hpp)
@@ -1309,6 +1401,7 @@ int qoc_eval_dev(qoc_ctx* c, const double* d_u, int order, double* d_J, double* 
 
 int qoc_propagate(qoc_ctx* c, const double* u, double* J_out) {
   if (c && c->ens_E) return ens_barred(c, "qoc_propagate");
+  if (c && c->ts_on) return ts_barred(c, "qoc_propagate");
   int r = check_ready(c);
   if (r) return r;
   if (!u) return fail(c, QOC_ERR_ARG, "u is null");
@@ -1325,6 +1418,7 @@ int qoc_propagate(qoc_ctx* c, const double* u, double* J_out) {
 
 int qoc_grape_sensitivity(qoc_ctx* c, const double* u, int order, const double* lambda_final, double* dJdu_out) {
   if (c && c->ens_E) return ens_barred(c, "qoc_grape_sensitivity");
+  if (c && c->ts_on) return ts_barred(c, "qoc_grape_sensitivity");
   int r = check_ready(c);
   if (r) return r;
   if (!c->fwd.valid) return fail(c, QOC_ERR_STATE, "grape_sensitivity called before propagate");
@@ -1508,6 +1602,7 @@ int qoc_eval_spline_dev(qoc_ctx* c, const double* d_c, int order, double* d_J, d
     return fail(c, QOC_ERR_STATE, "qoc_eval_spline_dev needs a device-side cost (TRACE or ZCAL)");
   if (order < 0 || order > 4) return fail(c, QOC_ERR_ARG, "dUkdp_order must be 1..4 or QOC_DUKDP_EXACT (got %d)", order);
   if ((r = ens_eval_check(c, order))) return r;
+  if ((r = ts_eval_check(c, order))) return r;
   const long long nuT = (long long)c->B * c->Nt * c->nu;
   const unsigned blocks = (unsigned)std::min<long long>((nuT + 255) / 256, 4096);
   hipLaunchKernelGGL(k_spline_u, dim3(blocks), dim3(256), 0, c->stream, c->B, c->Nt, c->ns, c->nu, c->d_Bs, d_c,
@@ -1544,6 +1639,7 @@ int qoc_eval_spline(qoc_ctx* c, const double* coef, int order, double* J_out, do
 int qoc_propagate_spline(qoc_ctx* c, const double* coef, double* J_out) {
   if (!c) return fail(nullptr, QOC_ERR_ARG, "null context");
   if (c->ens_E) return ens_barred(c, "qoc_propagate_spline");
+  if (c->ts_on) return ts_barred(c, "qoc_propagate_spline");
   if (!c->ns) return fail(c, QOC_ERR_STATE, "spline basis not set (qoc_set_spline_basis)");
   if (!coef) return fail(c, QOC_ERR_ARG, "c is null");
   HIPCHK(c, hipSetDevice(c->dev));
@@ -1566,6 +1662,7 @@ int qoc_propagate_spline(qoc_ctx* c, const double* coef, double* J_out) {
 int qoc_sensitivity_spline(qoc_ctx* c, const double* coef, int order, double* dJdc_out) {
   if (!c) return fail(nullptr, QOC_ERR_ARG, "null context");
   if (c->ens_E) return ens_barred(c, "qoc_sensitivity_spline");
+  if (c->ts_on) return ts_barred(c, "qoc_sensitivity_spline");
   if (!c->ns) return fail(c, QOC_ERR_STATE, "spline basis not set (qoc_set_spline_basis)");
   if (!coef) return fail(c, QOC_ERR_ARG, "c is null");
   int r = check_ready(c);
@@ -1618,6 +1715,7 @@ int qoc_set_propagation(qoc_ctx* c, int method, int nsub) {
 int qoc_propagate_envelope(qoc_ctx* c, int kind, const double* params, int np, double tgate, double dt, double* J_out,
                            double* x_out) {
   if (c && c->ens_E) return ens_barred(c, "qoc_propagate_envelope");
+  if (c && c->ts_on) return ts_barred(c, "qoc_propagate_envelope");
   int r = check_ready(c);
   if (r) return r;
   if (!params || np < 1 || np > 64) return fail(c, QOC_ERR_ARG, "bad parameter array");
@@ -1654,6 +1752,7 @@ int qoc_propagate_envelope(qoc_ctx* c, int kind, const double* params, int np, d
 static int env_eval_check(qoc_ctx* c, int kind, const void* params, int np, double tgate, double dt, const void* dJdp,
                           long long* nsteps) {
   if (c && c->ens_E) return ens_barred(c, "qoc_eval_envelope");
+  if (c && c->ts_on) return ts_barred(c, "qoc_eval_envelope");
   int r = check_ready(c);
   if (r) return r;
   if (!params || np < 1 || np > 64) return fail(c, QOC_ERR_ARG, "bad parameter array");

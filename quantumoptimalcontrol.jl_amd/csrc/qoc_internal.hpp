@@ -289,6 +289,14 @@ struct qoc_ctx {
   double2* d_ens_gseg = nullptr;     // B E x NB^2 x S x nblk complex G at the segment ends, and D behind it when penalised
   size_t ens_gseg_bytes = 0, ens_risk_bytes = 0;
   bool seg_attr_ens_half[2][5][2][2] = {};  // [NB - 2][order slot][forward, backward][penalised]: seg_attr for the ENS halves
+  // The gate duration as a per-seed variable (qoc_set_time_scale): while ts_on, qoc_eval_dev runs the segmented
+  // eval's TS instantiations (blkseg_eval_ts), which read τ_b from d_ts at launch and leave dJ_b/dτ_b behind it.  A
+  // setting of the context: it survives qoc_set_generators, qoc_set_x0 and qoc_set_cost.  Allocated by the setter
+  // (counted in dev_bytes), freed when the scale is cleared and at qoc_destroy.
+  bool ts_on = false;
+  bool ts_grad = false;              // d_ts + B holds an eval's dJ/dτ
+  double* d_ts = nullptr;            // 2 B: τ_b | dJ_b/dτ_b of the last eval under the scale
+  bool seg_attr_ts[2][5][3][2] = {};  // seg_attr for the TS instantiations
   int* h_flag = nullptr;             // host-mapped stale-u flag of the queued check (k_compare_u_flags)
   int flag_turn = 0;                 // which of the two device flags d_flag[0 / 1] the next queued check writes
   hipEvent_t flag_ev = nullptr;      // recorded after that copy
@@ -556,6 +564,11 @@ struct EnsPlan {
   size_t om_bytes = 0, gseg_bytes = 0;
 };
 EnsPlan blkseg_ens_plan(qoc_ctx* c, int E, const double* w, int kind, double param);
+// with a time scale set (qoc_ctx::ts_on): whether the segmented eval takes the eval (blkseg_ok; penalised blocks of 3
+// rows run as the two halves), and the eval: J, dJdu at fixed τ and dJ/dτ into d_ts + B.  Nothing lazy is kept and
+// the last backward's record stands.
+bool blkseg_ts_ok(const qoc_ctx* c, int order);
+int blkseg_eval_ts(qoc_ctx* c, int order, const double* d_u, double* d_J, double* d_dJdu);
 // the reference's split call form on the segmented eval: propagate = phases 0-2 (G at the segment ends to HBM),
 // grape_sensitivity = phase 3 (stale: the device flag of a stale-u check queued before it, or nullptr)
 bool blkseg_split_ok(const qoc_ctx* c);

@@ -390,19 +390,11 @@ int blkseg_eval_ens(qoc_ctx* c, int order, const double* d_u, double* d_J, doubl
   return QOC_OK;
 }
 
-// propagate on the segmented eval (the reference's f, examples/ipopt_callbacks_exp.jl:11-19): J, the λ_N coefficients
-// and G at every segment's end, x_k rebuilt on demand.  Applies where the fused eval does (any order: the forward half
-// has none) unless QOC_BLKSEG_SPLIT=0.
-bool blkseg_split_ok(const qoc_ctx* c) {
-  return !env_is("QOC_BLKSEG_SPLIT", "0") && blkseg_ok(c, 3);
-}
+bool blkseg_ts_ok(const qoc_ctx* c, int order) { return c->ts_on && c->ens_E == 0 && blkseg_ok(c, order); }
 
-int blkseg_forward(qoc_ctx* c, const double* d_u, double* d_J) {
-  const BlksegShape s = blkseg_shape(c);
-  int r = ensure_lazy_bufs(c);
-  if (r) return r;
-  // G at every segment's end, and behind it D when the eval is penalised
-  const size_t gcount = (size_t)c->B * s.S * c->nblk * c->blk_nb * c->blk_nb;
+// G (and D behind it when the eval is penalised) at every segment's end: the buffer the forward half writes
+static int blkseg_gseg_buf(qoc_ctx* c, const BlksegShape& s, size_t& gcount) {
+  gcount = (size_t)c->B * s.S * c->nblk * c->blk_nb * c->blk_nb;
   const size_t gbytes = (blkseg_pen(c) ? 2 : 1) * gcount * sizeof(double2);
   if (c->gseg_bytes < gbytes) {  // a new block layout (qoc_set_generators) or a penalty may need more
     if (c->d_gseg) {
@@ -416,6 +408,62 @@ int blkseg_forward(qoc_ctx* c, const double* d_u, double* d_J) {
     c->gseg_bytes = gbytes;
     c->dev_bytes += gbytes;
   }
+  return QOC_OK;
+}
+
+// One eval under a per-seed time scale (qoc_set_time_scale): the TS instantiations read τ_b from d_ts and write J,
+// dJdu at fixed τ and dJ/dτ (d_ts + B); one fused launch, or the two halves for penalised blocks of 3 rows (as
+// blkseg_eval).  u goes into d_u when the caller's buffer is another one.  Nothing lazy is kept (the k_blku_* rebuild
+// chains know nothing of τ), the last backward's record stands, and the launch's own epilogue leaves the best
+// (J, seed).
+int blkseg_eval_ts(qoc_ctx* c, int order, const double* d_u, double* d_J, double* d_dJdu) {
+  const BlksegShape s = blkseg_shape(c);
+  const bool halves = blkseg_pen(c) && c->blk_nb == 3;
+  size_t gcount = 0;
+  int r;
+  if (halves && (r = blkseg_gseg_buf(c, s, gcount))) return r;
+  BlksegParams sp;
+  if ((r = blkseg_params(c, s, sp))) return r;
+  sp.u = d_u;
+  sp.u_copy = d_u != c->d_u ? c->d_u : nullptr;
+  sp.J2 = d_J && d_J != c->d_J ? d_J : nullptr;
+  sp.dJdu = d_dJdu;
+  sp.tau = c->d_ts;
+  sp.dJdtau = c->d_ts + c->B;
+  const int mk = mark_begin(c, 2);
+  hipError_t e;
+  if (halves) {
+    sp.gseg = c->d_gseg;
+    sp.dseg = c->d_gseg + gcount;
+    e = blkseg_launch_ts(c, BLKSEG_FWD, 1, s, sp);
+    if (e == hipSuccess) {
+      sp.u_copy = nullptr;  // (written by the forward half)
+      sp.J2 = nullptr;
+      e = blkseg_launch_ts(c, BLKSEG_BWD, order, s, sp);
+    }
+  } else {
+    e = blkseg_launch_ts(c, BLKSEG_FUSED, order, s, sp);
+  }
+  mark_end(c, mk);
+  if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "k_blkseg_eval (time scale) launch: %s", hipGetErrorString(e));
+  c->jbest.ready = true;
+  c->ts_grad = true;
+  return QOC_OK;
+}
+
+// propagate on the segmented eval (the reference's f, examples/ipopt_callbacks_exp.jl:11-19): J, the λ_N coefficients
+// and G at every segment's end, x_k rebuilt on demand.  Applies where the fused eval does (any order: the forward half
+// has none) unless QOC_BLKSEG_SPLIT=0.
+bool blkseg_split_ok(const qoc_ctx* c) {
+  return !env_is("QOC_BLKSEG_SPLIT", "0") && blkseg_ok(c, 3);
+}
+
+int blkseg_forward(qoc_ctx* c, const double* d_u, double* d_J) {
+  const BlksegShape s = blkseg_shape(c);
+  int r = ensure_lazy_bufs(c);
+  if (r) return r;
+  size_t gcount = 0;
+  if ((r = blkseg_gseg_buf(c, s, gcount))) return r;
   BlksegParams sp;
   if ((r = blkseg_params(c, s, sp))) return r;
   sp.u = d_u;

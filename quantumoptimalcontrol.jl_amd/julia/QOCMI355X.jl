@@ -177,6 +177,38 @@ function member_weights(c::MI355XCache)
     return om
 end
 
+"""
+    set_time_scale!(cache, tau)
+
+Gate duration as a variable (include/qoc.h `qoc_set_time_scale`): the cache's pulse evolves under τ (A0 + Σ_j u_jk A_j),
+so its gate lasts τ times the nominal duration; `tau` finite and > 0, `nothing` clears it.  With it set the library
+evaluates J and dJ/du at that duration in `qoc_eval_dev` / `qoc_eval_spline` (built-in costs, as for the ensemble),
+leaves dJ/dτ at fixed u for `time_scale_grad`, and refuses `propagate` / `grape_sensitivity`.  It survives `upload!`.
+Like the rest of this shim the four wrappers are written against the ABI and have not been run (no `julia` where the
+library is built and tested).
+"""
+function set_time_scale!(c::MI355XCache, tau::Union{Nothing,Real})
+    if tau === nothing
+        check(ccall((:qoc_set_time_scale, libqoc), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), c.ctx, C_NULL), c.ctx)
+    else
+        t = [Float64(tau)]   # B = 1
+        check(ccall((:qoc_set_time_scale, libqoc), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), c.ctx, t), c.ctx)
+    end
+    return nothing
+end
+
+"""dJ/dτ of the last eval under the time scale (`qoc_get_time_scale_grad`); not run, see above."""
+function time_scale_grad(c::MI355XCache)
+    d = zeros(1)
+    check(ccall((:qoc_get_time_scale_grad, libqoc), Cint, (Ptr{Cvoid}, Ptr{Cdouble}), c.ctx, d), c.ctx)
+    return d[1]
+end
+
+"""Device pointers of τ and of dJ/dτ (`qoc_time_scale_dev`, `qoc_time_scale_grad_dev`; `C_NULL` when none is set), for
+callers that write τ on the library's stream between evals; not run, see above."""
+time_scale_device(c::MI355XCache) = ccall((:qoc_time_scale_dev, libqoc), Ptr{Cdouble}, (Ptr{Cvoid},), c.ctx)
+time_scale_grad_device(c::MI355XCache) = ccall((:qoc_time_scale_grad_dev, libqoc), Ptr{Cdouble}, (Ptr{Cvoid},), c.ctx)
+
 """States of the last propagate, fetched lazily (the reference returns cache.x, Nt+1 matrices)."""
 struct LazyStates <: AbstractVector{Matrix{ComplexF64}}
     c::MI355XCache

@@ -63,6 +63,10 @@ SIGNATURES = {
     "qoc_get_member_weights": (C.c_int, [_vp, _dp]),
     "qoc_member_weights_dev": (_vp, [_vp]),
     "qoc_member_grads_dev": (_vp, [_vp]),
+    "qoc_set_time_scale": (C.c_int, [_vp, _dp]),
+    "qoc_time_scale_dev": (_vp, [_vp]),
+    "qoc_get_time_scale_grad": (C.c_int, [_vp, _dp]),
+    "qoc_time_scale_grad_dev": (_vp, [_vp]),
     "qoc_set_x0": (C.c_int, [_vp, _dp, C.c_int]),
     "qoc_set_cost": (C.c_int, [_vp, C.c_int, _dp, C.c_double]),
     "qoc_set_state_penalty": (C.c_int, [_vp, _ip, C.c_int, _ip, C.c_int, C.c_double]),

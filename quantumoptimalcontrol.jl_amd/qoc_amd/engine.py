@@ -210,6 +210,34 @@ class GrapeEngine:
         left there."""
         return int(self._lib.qoc_member_grads_dev(self._h) or 0)
 
+    # ---- gate duration as a variable (include/qoc.h qoc_set_time_scale) -------------
+    def set_time_scale(self, tau):
+        """Seed b evolves under tau[b] (A0 + Σ_j u_jk A_j): its gate lasts tau[b] times the nominal duration, and
+        seeds of different durations share one launch (a gate-time sweep is one batch).  tau: B values, finite and
+        > 0, or None to clear.  eval_device / eval_spline / minimize_spline_device / allgather_best then work on
+        J at that duration, and every eval leaves dJ/dτ at fixed u in time_scale_grad().  propagate /
+        grape_sensitivity and the other split calls raise QOCError (QOC_ERR_UNSUPPORTED) until it is cleared."""
+        if tau is None:
+            self._chk(self._lib.qoc_set_time_scale(self._h, None))
+            return
+        t = np.ascontiguousarray(np.broadcast_to(np.asarray(tau, dtype=np.float64), (self.B,)))
+        self._chk(self._lib.qoc_set_time_scale(self._h, _ptr(t)))
+
+    def time_scale_grad(self) -> np.ndarray:
+        """dJ/dτ (B,) of the last eval under the time scale, at fixed u (synchronises)."""
+        out = np.zeros(self.B)
+        self._chk(self._lib.qoc_get_time_scale_grad(self._h, _ptr(out)))
+        return out
+
+    def time_scale_device(self) -> int:
+        """Device pointer of the B values of τ (0 when none is set).  They may be overwritten on the engine's stream
+        between evals; every eval reads them at launch, unchecked."""
+        return int(self._lib.qoc_time_scale_dev(self._h) or 0)
+
+    def time_scale_grad_device(self) -> int:
+        """Device pointer of the B values of dJ/dτ every eval under the time scale writes (0 when none is set)."""
+        return int(self._lib.qoc_time_scale_grad_dev(self._h) or 0)
+
     def set_x0(self, x0, per_seed: bool = False):
         x0 = np.asarray(x0, dtype=np.complex128)
         if per_seed:

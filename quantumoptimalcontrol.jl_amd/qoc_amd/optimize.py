@@ -69,6 +69,68 @@ class SplineGrape:
         return self._g.clone(), self._gj.clone()
 
 
+class SplineGrapeDuration:
+    """f + grad with the gate duration as one more variable per seed (``GrapeEngine.set_time_scale``), for the
+    host-driven ``minimize_batched`` / ``minimize_ticks``, which take per-variable bounds.
+
+    z = [c (ns * nu, SplineGrape's layout), τ] per seed, (B, ns * nu + 1);  f(z) = J(c; τ) + time_weight * τ and
+    grad = [Bs' transpose(dJdu), dJ/dτ + time_weight].  J is the engine's at τ times the nominal duration, state
+    penalty included; dJ/dτ is exact at every order.  Keep τ > 0 with a lower bound: the engine does not check values
+    written to its device buffer.
+
+    A device tensor z takes the device route: τ goes into the engine's own buffer (``time_scale_device``) and
+    dJ/dτ is read from ``time_scale_grad_device``, so nothing crosses to the host that ``SplineGrape.fg`` does not
+    move.  A host z (numpy or a CPU tensor) goes through ``set_time_scale`` / ``eval_spline`` / ``time_scale_grad``.
+    """
+
+    def __init__(self, engine, Bs, order: int = 3, time_weight: float = 0.0):
+        self.eng = engine
+        self.order = order
+        self.kappa = float(time_weight)
+        engine.set_spline_basis(Bs)
+        self.ns, self.nu, self.B = engine.ns, engine.nu, engine.B
+        self.nc = self.ns * self.nu
+        self.n = self.nc + 1
+        self.n_evals = 0
+        self._dev = None
+
+    def _device_buffers(self):
+        import torch
+        if not self.eng.time_scale_device():
+            self.eng.set_time_scale(np.ones(self.B))
+            self._dev = None
+        if self._dev is None:
+            dev = torch.device("cuda", self.eng.device)
+            J = torch.empty(self.B, dtype=torch.float64, device=dev)
+            G = torch.empty(self.B, self.nc, dtype=torch.float64, device=dev)
+            tau = torch.as_tensor(_DevView(self.eng.time_scale_device(), (self.B,), "<f8"), device=dev)
+            dtau = torch.as_tensor(_DevView(self.eng.time_scale_grad_device(), (self.B,), "<f8"), device=dev)
+            self._dev = (dev, J, G, tau, dtau)
+        return self._dev
+
+    def fg(self, z):
+        import torch
+        self.n_evals += 1
+        if isinstance(z, torch.Tensor) and z.is_cuda:
+            dev, J, G, tau, dtau = self._device_buffers()
+            c = z[:, :self.nc].contiguous()
+            tau.copy_(z[:, self.nc])
+            torch.cuda.current_stream(dev).synchronize()  # c and τ produced on torch's stream
+            self.eng.eval_spline_device(c.data_ptr(), self.order, J.data_ptr(), G.data_ptr())
+            self.eng.synchronize()
+            return J + self.kappa * z[:, self.nc], torch.cat([G, (dtau + self.kappa)[:, None]], 1)
+        zh = z.detach().cpu().numpy() if isinstance(z, torch.Tensor) else np.asarray(z, dtype=np.float64)
+        zh = zh.reshape(self.B, self.n)
+        tau = zh[:, self.nc]
+        self.eng.set_time_scale(tau)
+        # c[s + ns j] is reshape(c, ns, nu)[s, j]: eval_spline takes and returns (B, ns, nu)
+        J, dJdc = self.eng.eval_spline(np.transpose(zh[:, :self.nc].reshape(self.B, self.nu, self.ns), (0, 2, 1)), self.order)
+        dtau = np.asarray(self.eng.time_scale_grad(), dtype=np.float64)
+        g = np.concatenate([np.transpose(np.asarray(dJdc), (0, 2, 1)).reshape(self.B, self.nc),
+                            (dtau + self.kappa)[:, None]], 1)
+        return torch.from_numpy(np.asarray(J) + self.kappa * tau), torch.from_numpy(g)
+
+
 def spline_constraints_torch(c, ns: int, nu: int):
     """Reference (torch) form of g = [norm(c), norm(diff(c, dims=1))] and its Jacobian (B, 2, nc)."""
     import torch
