@@ -490,7 +490,8 @@ int qoc_opt_tell_dev(qoc_opt* opt, void* stream, const double* d_f, const double
  * groups of poll_every (<= 0: 16); after each group the host waits on one event and reads the mirrored count of
  * finished seeds.  Stops when all seeds are done or after max_ticks ticks, QOC_OK either way (qoc_opt_result tells
  * which).  Then one closing eval at the final iterates: the context's u, J, lazy states and best-(J, seed) epilogue
- * (qoc_allgather_best) belong to the result.  d_c (B x ns x nu, device): the starts in, the final iterates out.
+ * (qoc_allgather_best) belong to the result; with max_ticks = 0 no seed takes an eval and the result's f is the
+ * closing eval's, at the clamped starts.  d_c (B x ns x nu, device): the starts in, the final iterates out.
  * ticks_out: the ticks the slowest seed used.  QOC_ERR_STATE without a spline basis, QOC_ERR_ARG when B or n differ. */
 int qoc_minimize_spline_dev(qoc_ctx* ctx, qoc_opt* opt, double* d_c, long long max_ticks, int poll_every,
                             long long* ticks_out);

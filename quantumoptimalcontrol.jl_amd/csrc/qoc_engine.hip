@@ -2326,6 +2326,9 @@ int qoc_minimize_spline_dev(qoc_ctx* c, qoc_opt* o, double* d_c, long long max_t
   }
   // closing eval at the final iterates: u, J, the lazy states and the best-(J, seed) epilogue are the result's
   if ((r = qoc_eval_spline_dev(c, o->st.x, order, c->d_J, nullptr))) return r;
+  // no tick ran (max_ticks = 0): no seed has taken an eval, so the result's f is the closing eval's
+  if (ticks == 0)
+    HIPCHK(c, hipMemcpyAsync(o->st.f, c->d_J, (size_t)c->B * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_c, o->st.x, (size_t)c->B * o->P.n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   std::vector<int> ev(c->B);
   HIPCHK(c, hipMemcpyAsync(ev.data(), o->st.evals, (size_t)c->B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
