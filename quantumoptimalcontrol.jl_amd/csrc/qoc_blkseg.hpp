@@ -546,6 +546,68 @@ __device__ __forceinline__ void sk2_vmul(const double (&v)[4], const double (&p)
   t[3] = fma(v[0], p[3], fma(v[1], p[2], fma(-v[2], p[1], v[3] * p[0])));
 }
 
+// ---- phase 3 of the phase-free loops in the Pauli basis (orders 1..3, no penalty) ----
+// V = v0 I + i n.σ with v = (v0, n3, n2, n1) as sk2_form_v returns it, and Ĝ = g0 I + g.σ (g0 complex, g a complex
+// 3-vector), carried doubled as gp = (2 Re g0, 2 Im g0, 2 Re g[1..3], 2 Im g[1..3]): every map below is linear in Ĝ,
+// and sk2_contract_pauli takes K doubled.  With d = n.g and t = n x g
+//   K = V^H Ĝ:    k0 = v0 g0 - i d,  k = v0 g - i g0 n + t
+//   Ĝ' = V^H Ĝ V: g0' = g0 (nothing to compute),  g' = g + 2 (v0 t + n x t)   (|V| = 1 used: v0² + |n|² = 1)
+// t is shared between K and the rotation and no matrix is formed: 30 + 22 fp64 instructions at order 3 against the
+// two general 2 x 2 products' 64 and the seven additions that turned K into its Pauli components (DESIGN.md §4 round
+// 10; checked against the matrix products in tests/test_blkseg_pauli_algebra.py).
+// The doubled Pauli components of a 2 x 2 matrix (row-major entries)
+__device__ __forceinline__ void sk2_pauli_of(const double (&mr)[4], const double (&mi)[4], double (&gp)[8]) {
+  gp[0] = mr[0] + mr[3];
+  gp[1] = mi[0] + mi[3];
+  gp[2] = mr[1] + mr[2];
+  gp[3] = mi[2] - mi[1];
+  gp[4] = mr[0] - mr[3];
+  gp[5] = mi[1] + mi[2];
+  gp[6] = mr[1] - mr[2];
+  gp[7] = mi[0] - mi[3];
+}
+// t = n x g (tc = Re t[1..3], Im t[1..3]) and the doubled Pauli components of K = V^H Ĝ that the order-ORD contraction
+// reads, kc = (Re k0, Im k0, Re k1, Im k1, Re k2, Im k2, Im k3): order 1 Im k1, Im k2; order 2 also Re k0, Re k1,
+// Re k2; order 3 also Im k0, Im k3.  The others are left alone.
+template <int ORD>
+__device__ __forceinline__ void sk2_pauli_k(const double (&v)[4], const double (&gp)[8], double (&tc)[6],
+                                            double (&kc)[7]) {
+  const double v0 = v[0], n1 = v[3], n2 = v[2], n3 = v[1];
+  const double* a = gp + 1;  // a[1..3] = 2 Re g, b[1..3] = 2 Im g
+  const double* b = gp + 4;
+  tc[0] = fma(n2, a[3], -n3 * a[2]);
+  tc[1] = fma(n3, a[1], -n1 * a[3]);
+  tc[2] = fma(n1, a[2], -n2 * a[1]);
+  tc[3] = fma(n2, b[3], -n3 * b[2]);
+  tc[4] = fma(n3, b[1], -n1 * b[3]);
+  tc[5] = fma(n1, b[2], -n2 * b[1]);
+  kc[3] = fma(v0, b[1], fma(-gp[0], n1, tc[3]));
+  kc[5] = fma(v0, b[2], fma(-gp[0], n2, tc[4]));
+  if constexpr (ORD >= 2) {
+    const double di = fma(n3, b[3], fma(n2, b[2], n1 * b[1]));
+    kc[0] = fma(v0, gp[0], di);
+    kc[2] = fma(v0, a[1], fma(gp[1], n1, tc[0]));
+    kc[4] = fma(v0, a[2], fma(gp[1], n2, tc[1]));
+  }
+  if constexpr (ORD >= 3) {
+    const double dr = fma(n3, a[3], fma(n2, a[2], n1 * a[1]));
+    kc[1] = fma(v0, gp[1], -dr);
+    kc[6] = fma(v0, b[3], fma(-gp[0], n3, tc[5]));
+  }
+}
+// g' = g + 2 (v0 t + n x t) on the six reals of g (gn = gp[2..7] rotated; g0 stays)
+__device__ __forceinline__ void sk2_pauli_rot(const double (&v)[4], const double (&tc)[6], const double (&gp)[8],
+                                              double (&gn)[6]) {
+  const double w0 = 2.0 * v[0], m1 = 2.0 * v[3], m2 = 2.0 * v[2], m3 = 2.0 * v[1];
+#pragma unroll
+  for (int c = 0; c < 2; ++c) {  // real and imaginary parts
+    const double t1 = tc[3 * c], t2 = tc[3 * c + 1], t3 = tc[3 * c + 2];
+    gn[3 * c] = fma(m2, t3, fma(-m3, t2, fma(w0, t1, gp[2 + 3 * c])));
+    gn[3 * c + 1] = fma(m3, t1, fma(-m1, t3, fma(w0, t2, gp[3 + 3 * c])));
+    gn[3 * c + 2] = fma(m1, t2, fma(-m2, t1, fma(w0, t3, gp[4 + 3 * c])));
+  }
+}
+
 // R <- R X in place, X skew-Hermitian (x0, x1, yr + i yq): 12 FMAs per row instead of 16
 __device__ __forceinline__ void sk2_rx(double (&Rr)[4], double (&Ri)[4], const Sk2& x) {
 #pragma unroll
@@ -608,6 +670,39 @@ __device__ __forceinline__ void sk2_contract(const Sk2& x, const Sk2& e1, const 
 // the K components below can stay doubled: 2 k0 = K00 + K11, ...) times the trace's -1/2 (sk2_pauli2).
 // CX: X's diagonal is the same in every slice (zero-diagonal controls, zero control shifts): x0, x3 and x0² come
 // precomputed (x0c, x3c, x02c: the same values)
+// The CX traces from K's doubled Pauli components as they are, kc = (Re k0, Im k0, Re k1, Im k1, Re k2, Im k2, Im k3)
+// (sk2_pauli_k forms them without a matrix); order 1 reads Im k1, Im k2, order 2 also Re k0, Re k1, Re k2, order 3 all.
+// Zero-diagonal controls without shifts: a1[0] = a1[3] = a2[0] = a2[3] = 0 exactly, so m0 and m3 (and Re d, 2 Re k3
+// and al0, which feed nothing else) are not formed: they entered the sums as products with exact zeros added to
+// finite values, so the traces are the same bits
+template <int ORD>
+__device__ __forceinline__ void sk2_contract_pauli_k(double x1, double x2, const double (&a1)[4],
+                                                     const double (&a2)[4], const double (&kc)[7], double& acc1,
+                                                     double& acc2, double x0c, double x3c, double x02c) {
+  static_assert(ORD >= 1 && ORD <= 3, "Pauli form for orders 1..3");
+  const double k1i = kc[3], k2i = kc[5];
+  double m1, m2;
+  if constexpr (ORD == 1) {
+    m1 = k1i;
+    m2 = k2i;
+  } else {
+    const double k0r = kc[0], k1r = kc[2], k2r = kc[4];
+    if constexpr (ORD == 2) {
+      m1 = fma(x0c, k1r, fma(k0r, x1, k1i));
+      m2 = fma(x0c, k2r, fma(k0r, x2, k2i));
+    } else {
+      const double k0i = kc[1], k3i = kc[6];
+      const double di = fma(x3c, k3i, fma(x2, k2i, x1 * k1i));
+      const double w = fma(x3c, x3c, fma(x2, x2, x1 * x1));
+      const double al1 = fma(-0.5, x02c, fma(-1.0 / 6.0, w, 1.0));
+      const double c = fma(-x0c, k0i, fma(-1.0 / 3.0, di, k0r));
+      m1 = fma(al1, k1i, fma(x0c, k1r, c * x1));
+      m2 = fma(al1, k2i, fma(x0c, k2r, c * x2));
+    }
+  }
+  acc1 = fma(a1[2], m2, a1[1] * m1);
+  acc2 = fma(a2[2], m2, a2[1] * m1);
+}
 template <int ORD, bool CX = false>
 __device__ __forceinline__ void sk2_contract_pauli(const Sk2& x, const double (&a1)[4], const double (&a2)[4],
                                                    const double (&Kr)[4], const double (&Ki)[4], double& acc1,
@@ -617,30 +712,13 @@ __device__ __forceinline__ void sk2_contract_pauli(const Sk2& x, const double (&
   // doubled Pauli components of K: 2k0 = K00 + K11, 2k1 = K01 + K10, 2k2 = i (K01 - K10), 2k3 = K00 - K11
   const double k0i = Ki[0] + Ki[3], k1i = Ki[1] + Ki[2], k2i = Kr[1] - Kr[2], k3i = Ki[0] - Ki[3];
   if constexpr (CX) {
-    // zero-diagonal controls without shifts: a1[0] = a1[3] = a2[0] = a2[3] = 0 exactly, so m0 and m3 (and Re d, 2 Re k3
-    // and al0, which feed nothing else) are not formed: they entered the sums as products with exact zeros added to
-    // finite values, so the traces are the same bits
-    double m1, m2;
-    if constexpr (ORD == 1) {
-      m1 = k1i;
-      m2 = k2i;
-    } else {
-      const double k0r = Kr[0] + Kr[3], k1r = Kr[1] + Kr[2], k2r = Ki[2] - Ki[1];
-      const double x1 = x.q, x2 = x.r;
-      if constexpr (ORD == 2) {
-        m1 = fma(x0c, k1r, fma(k0r, x1, k1i));
-        m2 = fma(x0c, k2r, fma(k0r, x2, k2i));
-      } else {
-        const double di = fma(x3c, k3i, fma(x2, k2i, x1 * k1i));
-        const double w = fma(x3c, x3c, fma(x2, x2, x1 * x1));
-        const double al1 = fma(-0.5, x02c, fma(-1.0 / 6.0, w, 1.0));
-        const double c = fma(-x0c, k0i, fma(-1.0 / 3.0, di, k0r));
-        m1 = fma(al1, k1i, fma(x0c, k1r, c * x1));
-        m2 = fma(al1, k2i, fma(x0c, k2r, c * x2));
-      }
+    double kc[7] = {0.0, k0i, 0.0, k1i, 0.0, k2i, k3i};
+    if constexpr (ORD >= 2) {
+      kc[0] = Kr[0] + Kr[3];
+      kc[2] = Kr[1] + Kr[2];
+      kc[4] = Ki[2] - Ki[1];
     }
-    acc1 = fma(a1[2], m2, a1[1] * m1);
-    acc2 = fma(a2[2], m2, a2[1] * m1);
+    sk2_contract_pauli_k<ORD>(x.q, x.r, a1, a2, kc, acc1, acc2, x0c, x3c, x02c);
     return;
   }
   double m0, m1, m2, m3;  // 2 Im m
@@ -1925,19 +2003,67 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
       reduce(jj, !SEL || act ? acc1 : 0.0, !SEL || act ? acc2 : 0.0);
     }
   };
+  // The same step of the phase-free loops in the Pauli basis (PAU: orders 1..3 without the penalty, whose step works
+  // on the matrices G and D): Ĝ as gp, K's components and the rotation from sk2_pauli_k / sk2_pauli_rot.  g0 (gp[0..1])
+  // is the same in every slice.  The fused, backward, ensemble and time-scale instances all take this form.
+  constexpr bool PAU = NB == 2 && !PEN && ORD >= 1 && ORD <= 3;
+  double gp[8];
+  auto p3_pauli = [&](int jj, auto SEL_, auto K_, const double2* upre = nullptr) {
+    constexpr bool SEL = decltype(SEL_)::value;
+    constexpr int KS = decltype(K_)::value;
+    if constexpr (PAU) {
+      const int k = kb + jj;
+      const bool act = !SEL || (sact && k < ke);
+      const double* r = SEL ? rec + 4 * (size_t)(act ? k : 0) : reck + 4 * (size_t)jj;
+      const double2 u = upre ? *upre : *reinterpret_cast<const double2*>(r + 2);
+      Sk2 ah;
+      double vv[4], tc[6], kc[7], gn[6];
+      sk2_form_v<KS>(gk, u, za0, ah, vv);
+      sk2_pauli_k<ORD>(vv, gp, tc, kc);
+      sk2_pauli_rot(vv, tc, gp, gn);
+#pragma unroll
+      for (int e = 0; e < 6; ++e) gp[2 + e] = !SEL || act ? gn[e] : gp[2 + e];
+      if constexpr (TS) {
+        // tr(X_k Ĝ_k) = i (x0 2 g0 + x . 2 g) on the doubled components, X = i (x0 I + x.σ), x = (q, r, x3): the
+        // quantity the matrix form sums.  Lanes without a segment are dropped at the reduction.
+        const double t_re = -fma(ah.q, gn[3], fma(ah.r, gn[4], fma(zx3, gn[5], zx0 * gp[1])));
+        const double t_im = fma(ah.q, gn[0], fma(ah.r, gn[1], fma(zx3, gn[2], zx0 * gp[0])));
+        tsr += !SEL || act ? t_re : 0.0;
+        tsi += !SEL || act ? t_im : 0.0;
+      }
+      double acc1, acc2;
+      sk2_contract_pauli_k<ORD>(ah.q, ah.r, pa1, pa2, kc, acc1, acc2, zx0, zx3, zx02);
+      reduce(jj, !SEL || act ? acc1 : 0.0, !SEL || act ? acc2 : 0.0);
+    }
+  };
   auto loop3z = [&](auto K_, auto ZD_) {
+    constexpr bool PZ = PAU && decltype(ZD_)::value;
+    auto p3 = [&](int jj, auto SEL_, const double2* upre = nullptr) {
+      if constexpr (PZ) p3_pauli(jj, SEL_, K_, upre);
+      else p3_fast(jj, SEL_, K_, ZD_, upre);
+    };
+    // Ĝ (behind the z̄ turn, fused or back from HBM) to its Pauli components, once per lane; nothing below reads G
+    if constexpr (PAU) {
+      if constexpr (PZ) sk2_pauli_of(Gr, Gi, gp);
+    }
     // the steps at and above Lf first, with the selects (none when Lf = L), then the rest in a loop of their own
     int jj = L - 1;
     for (; jj >= Lf; --jj) {
       if (turns) seg_turn(grp, ngrp, jj);
       sprog.step(L + (L - 1 - jj));
-      p3_fast(jj, std::true_type(), K_, ZD_);
+      p3(jj, std::true_type());
     }
     // ZD: the slice's controls are read one step ahead (the next step's while this one runs: the read's latency
     // stood at the head of every step), the last step reads its own again
     constexpr bool PRE = decltype(ZD_)::value;
     double2 un = make_double2(0.0, 0.0);
-    if (PRE && jj >= 0) un = *reinterpret_cast<const double2*>(reck + 4 * (size_t)jj + 2);
+    if (PRE && jj >= 0) {
+      un = *reinterpret_cast<const double2*>(reck + 4 * (size_t)jj + 2);
+      // This first read is waited for here, once, in front of the loop.  Left pending into the loop's head it made
+      // the compiler wait at the top of every step, in front of the first formation FMA, for everything but the newest
+      // read: the partner's count of SegProg::step, just issued, among it.
+      __builtin_amdgcn_s_waitcnt(0xc07f);  // lgkmcnt(0), the other counters left alone
+    }
     for (; jj >= 0; --jj) {
       if (turns) seg_turn(grp, ngrp, jj);
       sprog.step(L + (L - 1 - jj));
@@ -1946,7 +2072,7 @@ __global__ __launch_bounds__(64 * WMAX) void k_blkseg_eval(const TChainArgs g, c
         un = *reinterpret_cast<const double2*>(reck + 4 * (size_t)max(jj - 1, 0) + 2);
         __builtin_amdgcn_sched_barrier(0);
       }
-      p3_fast(jj, std::false_type(), K_, ZD_, PRE ? &uc : nullptr);
+      p3(jj, std::false_type(), PRE ? &uc : nullptr);
     }
   };
   auto loop3 = [&](auto K_) {
