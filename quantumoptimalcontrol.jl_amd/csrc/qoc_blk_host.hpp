@@ -28,8 +28,7 @@ static inline hipError_t blk_lds_attr(K kern, size_t lds) {
 // d_coef_mu (allocated on first use): the λ_N coefficients of an eval or backward that leaves μ_k in d_L
 static inline int blk_coef_mu(qoc_ctx* c) {
   if (c->d_coef_mu) return QOC_OK;
-  HIPCHK(c, hipMalloc((void**)&c->d_coef_mu, (size_t)c->B * 2 * c->m_user * sizeof(cx<double>)));
-  c->dev_bytes += (size_t)c->B * 2 * c->m_user * sizeof(cx<double>);
+  HIPCHK(c, c->d_coef_mu.alloc((size_t)c->B * 2 * c->m_user * sizeof(cx<double>)));
   return QOC_OK;
 }
 

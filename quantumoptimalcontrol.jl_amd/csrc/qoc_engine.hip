@@ -33,13 +33,9 @@ int upload_complex(qoc_ctx* ctx, const double* host, void* dev, size_t nelem) {
     HIPCHK(ctx, hipMemcpyAsync(dev, host, nelem * 16, hipMemcpyHostToDevice, ctx->stream));
     return QOC_OK;
   }
-  if (nelem > ctx->stage_elems) {
-    if (ctx->d_stage) hipFree(ctx->d_stage);
-    HIPCHK(ctx, hipMalloc(&ctx->d_stage, nelem * 16));
-    ctx->stage_elems = nelem;
-  }
+  HIPCHK(ctx, ctx->d_stage.grow(nelem * 16));
   HIPCHK(ctx, hipMemcpyAsync(ctx->d_stage, host, nelem * 16, hipMemcpyHostToDevice, ctx->stream));
-  hipLaunchKernelGGL((k_cvt_in<T>), dim3(256), dim3(256), 0, ctx->stream, (const cx<double>*)ctx->d_stage,
+  hipLaunchKernelGGL((k_cvt_in<T>), dim3(256), dim3(256), 0, ctx->stream, ctx->d_stage.as<const cx<double>>(),
                      (cx<T>*)dev, nelem);
   HIPCHK(ctx, hipGetLastError());
   return QOC_OK;
@@ -54,13 +50,9 @@ int download(qoc_ctx* ctx, const void* dev, double* host, size_t nelem) {
   if (ctx->prec == QOC_FP64) {
     HIPCHK(ctx, hipMemcpyAsync(host, dev, nelem * 16, hipMemcpyDeviceToHost, ctx->stream));
   } else {
-    if (nelem > ctx->stage_elems) {
-      if (ctx->d_stage) hipFree(ctx->d_stage);
-      HIPCHK(ctx, hipMalloc(&ctx->d_stage, nelem * 16));
-      ctx->stage_elems = nelem;
-    }
+    HIPCHK(ctx, ctx->d_stage.grow(nelem * 16));
     hipLaunchKernelGGL((k_cvt_out<float>), dim3(256), dim3(256), 0, ctx->stream, (const cx<float>*)dev,
-                       (cx<double>*)ctx->d_stage, nelem);
+                       ctx->d_stage.as<cx<double>>(), nelem);
     HIPCHK(ctx, hipGetLastError());
     HIPCHK(ctx, hipMemcpyAsync(host, ctx->d_stage, nelem * 16, hipMemcpyDeviceToHost, ctx->stream));
   }
@@ -409,7 +401,7 @@ int backward(qoc_ctx* c, int order, double* d_dJdu, const int* stale = nullptr) 
 // one launch: its device flag (returned in *dflag, for launches queued behind it) and the host-mapped flag c->h_flag,
 // read at c->flag_ev (wait_stale_check).  The two device flags take turns, each check zeroing the next one's.
 int queue_stale_check(qoc_ctx* c, const double* d_u, const int** dflag) {
-  if (!c->h_flag) HIPCHK(c, hipHostMalloc((void**)&c->h_flag, sizeof(int), hipHostMallocMapped | hipHostMallocCoherent));
+  if (!c->h_flag) HIPCHK(c, c->h_flag.alloc(sizeof(int)));
   if (!c->flag_ev) HIPCHK(c, hipEventCreateWithFlags(&c->flag_ev, hipEventDisableTiming));
   int* hdev = nullptr;
   HIPCHK(c, hipHostGetDevicePointer((void**)&hdev, c->h_flag, 0));
@@ -479,25 +471,18 @@ static int ts_eval_check(qoc_ctx* c, int order) {
 static void ts_clear(qoc_ctx* c) {
   if (c->d_ts) {
     if (c->stream) hipStreamSynchronize(c->stream);
-    hipFree(c->d_ts);
-    c->d_ts = nullptr;
-    c->dev_bytes -= (size_t)2 * c->B * sizeof(double);
+    c->d_ts.release();
   }
   c->ts_on = c->ts_grad = false;
 }
 // drops the ensemble and its workspace (the stream is drained first: a queued eval may still read them)
 static void ens_clear(qoc_ctx* c) {
-  if (!c->ens_E && !c->ens_bytes && !c->ens_risk_bytes) return;
+  if (!c->ens_E && !c->d_ens_gtab && !c->d_ens_om && !c->d_ens_gseg) return;
   if (c->stream) hipStreamSynchronize(c->stream);
-  for (void* p : {(void*)c->d_ens_gtab, (void*)c->d_ens_prm, (void*)c->d_ens_w, (void*)c->d_ens_J, (void*)c->d_ens_coef,
-                  (void*)c->d_ens_g, (void*)c->d_ens_om, (void*)c->d_ens_gseg})
-    if (p) hipFree(p);
-  c->d_ens_gtab = nullptr;
-  c->d_ens_prm = c->d_ens_w = c->d_ens_J = c->d_ens_g = c->d_ens_om = nullptr;
-  c->d_ens_coef = nullptr;
-  c->d_ens_gseg = nullptr;
-  c->dev_bytes -= c->ens_bytes + c->ens_risk_bytes;
-  c->ens_bytes = c->ens_risk_bytes = c->ens_gseg_bytes = 0;
+  for (DevBufBase* b : {(DevBufBase*)&c->d_ens_gtab, (DevBufBase*)&c->d_ens_prm, (DevBufBase*)&c->d_ens_w,
+                        (DevBufBase*)&c->d_ens_J, (DevBufBase*)&c->d_ens_coef, (DevBufBase*)&c->d_ens_g,
+                        (DevBufBase*)&c->d_ens_om, (DevBufBase*)&c->d_ens_gseg})
+    b->release();
   c->ens_last_route = 0;
   c->h_ens_w.clear();
   c->ens_E = 0;
@@ -546,30 +531,28 @@ int qoc_create(qoc_ctx** out, int device, int N, int m, int nu, int Nt, int B, i
   if ((e = hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking)) != hipSuccess) return bail(e, "stream");
   const size_t NN = (size_t)N * N, Nm = (size_t)N * m;
   struct {
-    void** p;
+    DevBufBase* b;
     size_t bytes;
   } allocs[] = {
       {&c->d_A, (nu + 1) * NN * c->esz},
       {&c->d_x0, (size_t)B * Nm * c->esz},
       {&c->d_Xt, Nm * c->esz},
-      {(void**)&c->d_pmask, Nm},
-      {(void**)&c->d_u, (size_t)B * nu * Nt * sizeof(double) + 16},  // + 16: slack past the last control
+      {&c->d_pmask, Nm},
+      {&c->d_u, (size_t)B * nu * Nt * sizeof(double) + 16},  // + 16: slack past the last control
       {&c->d_U, (size_t)B * Nt * NN * c->esz},
       {&c->d_X, (size_t)B * (Nt + 1) * Nm * c->esz},
       {&c->d_L, (size_t)B * (Nt + 1) * Nm * c->esz},
-      {(void**)&c->d_J, (size_t)B * sizeof(double)},
-      {(void**)&c->d_coef, (size_t)B * 2 * m * sizeof(cx<double>)},
-      {(void**)&c->d_rsec, (size_t)N},
-      {(void**)&c->d_dJdu, (size_t)B * nu * Nt * sizeof(double)},
-      {(void**)&c->d_flag, 2 * sizeof(int)},  // [0] the synchronous checks, [0] / [1] in turns the queued ones
-      {(void**)&c->d_hist, 13 * 64 * sizeof(unsigned long long)},
-      {(void**)&c->d_sink, TCHAIN_SINK * sizeof(double)},
-      {(void**)&c->d_ps, ((size_t)std::max<long long>((long long)B * Nt, 16384) + 1) * sizeof(int)},
+      {&c->d_J, (size_t)B * sizeof(double)},
+      {&c->d_coef, (size_t)B * 2 * m * sizeof(cx<double>)},
+      {&c->d_rsec, (size_t)N},
+      {&c->d_dJdu, (size_t)B * nu * Nt * sizeof(double)},
+      {&c->d_flag, 2 * sizeof(int)},  // [0] the synchronous checks, [0] / [1] in turns the queued ones
+      {&c->d_hist, 13 * 64 * sizeof(unsigned long long)},
+      {&c->d_sink, TCHAIN_SINK * sizeof(double)},
+      {&c->d_ps, ((size_t)std::max<long long>((long long)B * Nt, 16384) + 1) * sizeof(int)},
   };
-  for (auto& a : allocs) {
-    if ((e = hipMalloc(a.p, a.bytes)) != hipSuccess) return bail(e, "hipMalloc");
-    c->dev_bytes += a.bytes;
-  }
+  for (auto& a : allocs)
+    if ((e = a.b->alloc(a.bytes)) != hipSuccess) return bail(e, "hipMalloc");
   if ((e = hipMemset(c->d_flag, 0, 2 * sizeof(int))) != hipSuccess) return bail(e, "hipMemset");
   {
     int ncu = 0;
@@ -584,15 +567,13 @@ int qoc_create(qoc_ctx** out, int device, int N, int m, int nu, int Nt, int B, i
   c->grad_gemm = !c->grad_rr && !c->big && N >= 32 && nu <= 8 && !env_kernel;
   if (c->grad_rr) {
     const size_t cols = (size_t)B * (Nt + 1) * m;
-    if ((e = hipMalloc(&c->d_gws, 2 * (size_t)N * cols * c->esz)) != hipSuccess) return bail(e, "hipMalloc");
-    c->dev_bytes += 2 * (size_t)N * cols * c->esz;
+    if ((e = c->d_gws.alloc(2 * (size_t)N * cols * c->esz)) != hipSuccess) return bail(e, "hipMalloc");
   }
   if (c->grad_gemm) {
     const size_t cols = (size_t)B * (Nt + 1) * m;
-    if ((e = hipMalloc(&c->d_AH, (nu + 1) * NN * c->esz)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc(&c->d_Cst, nu * NN * c->esz)) != hipSuccess) return bail(e, "hipMalloc");
-    if ((e = hipMalloc(&c->d_gws, 6 * (size_t)N * cols * c->esz)) != hipSuccess) return bail(e, "hipMalloc");
-    c->dev_bytes += (2 * nu + 1) * NN * c->esz + 6 * (size_t)N * cols * c->esz;
+    if ((e = c->d_AH.alloc((nu + 1) * NN * c->esz)) != hipSuccess) return bail(e, "hipMalloc");
+    if ((e = c->d_Cst.alloc(nu * NN * c->esz)) != hipSuccess) return bail(e, "hipMalloc");
+    if ((e = c->d_gws.alloc(6 * (size_t)N * cols * c->esz)) != hipSuccess) return bail(e, "hipMalloc");
   }
   {
     const TShape sh = tchain_shape(N, m, precision == QOC_FP64);
@@ -604,11 +585,9 @@ int qoc_create(qoc_ctx** out, int device, int N, int m, int nu, int Nt, int B, i
     if (c->tchain_ok) {
       const size_t bytes[3] = {(nu + 1) * NN * c->esz, (size_t)B * Nt * sizeof(TStep),
                                TERM_SLOTS * sizeof(unsigned long long)};
-      void** ptrs[3] = {&c->d_At, (void**)&c->d_steps, (void**)&c->d_terms};
-      for (int i = 0; i < 3; ++i) {
-        if ((e = hipMalloc(ptrs[i], bytes[i])) != hipSuccess) return bail(e, "hipMalloc");
-        c->dev_bytes += bytes[i];
-      }
+      DevBufBase* bufs[3] = {&c->d_At, &c->d_steps, &c->d_terms};
+      for (int i = 0; i < 3; ++i)
+        if ((e = bufs[i]->alloc(bytes[i])) != hipSuccess) return bail(e, "hipMalloc");
       hipMemset(c->d_terms, 0, TERM_SLOTS * sizeof(unsigned long long));
     }
   }
@@ -624,10 +603,8 @@ int qoc_create(qoc_ctx** out, int device, int N, int m, int nu, int Nt, int B, i
     ch = std::min<long long>(ch, 16384);
     if (env_set("QOC_CHUNK")) ch = std::max(1, std::min<int>(env_int("QOC_CHUNK", 0), (int)std::min<long long>(units, 16384)));
     c->chunk = (int)ch;
-    if ((e = hipMalloc(&c->d_ws, (size_t)ch * per_item)) != hipSuccess) return bail(e, "hipMalloc (workspace)");
-    if ((e = hipMalloc((void**)&c->d_red, ((size_t)ch + 8) * sizeof(double))) != hipSuccess)
-      return bail(e, "hipMalloc");
-    c->dev_bytes += (size_t)ch * per_item + ((size_t)ch + 8) * sizeof(double);
+    if ((e = c->d_ws.alloc((size_t)ch * per_item)) != hipSuccess) return bail(e, "hipMalloc (workspace)");
+    if ((e = c->d_red.alloc(((size_t)ch + 8) * sizeof(double))) != hipSuccess) return bail(e, "hipMalloc");
   }
   hipMemset(c->d_pmask, 0, Nm);
   hipMemset(c->d_hist, 0, 13 * 64 * sizeof(unsigned long long));
@@ -653,31 +630,10 @@ void qoc_destroy(qoc_ctx* c) {
   if (!c) return;
   hipSetDevice(c->dev);
   if (c->stream) hipStreamSynchronize(c->stream);
+  if (c->stream2) hipStreamSynchronize(c->stream2);
   if (c->comm && rccl().commDestroy) rccl().commDestroy(c->comm);
-  if (c->d_best) hipFree(c->d_best);
-  if (c->d_done) hipFree(c->d_done);
-  if (c->d_tcoef) hipFree(c->d_tcoef);
-  if (c->d_coef_mu) hipFree(c->d_coef_mu);
-  if (c->d_brow) hipFree(c->d_brow);
-  if (c->d_gtab) hipFree(c->d_gtab);
-  if (c->d_wrow) hipFree(c->d_wrow);
-  if (c->d_wrow_live) hipFree(c->d_wrow_live);
-  if (c->d_dead_rows) hipFree(c->d_dead_rows);
-  if (c->d_gc_part) hipFree(c->d_gc_part);
-  if (c->d_gseg) hipFree(c->d_gseg);
-  ens_clear(c);
-  ts_clear(c);
-  if (c->d_blkp_ctab) hipFree(c->d_blkp_ctab);
-  if (c->d_blkp_M) hipFree(c->d_blkp_M);
-  if (c->d_blkp_ph) hipFree(c->d_blkp_ph);
-  if (c->d_minmax) hipFree(c->d_minmax);
-  if (c->h_minmax) hipHostFree(c->h_minmax);
-  if (c->h_flag) hipHostFree(c->h_flag);
+  c->mem.release_all();
   if (c->flag_ev) hipEventDestroy(c->flag_ev);
-  void* ptrs[] = {c->d_A, c->d_x0, c->d_Xt, c->d_pmask, c->d_u,    c->d_U,    c->d_X, c->d_L, c->d_u_lam, c->d_coef_lam, c->d_blkU, c->d_J_scr, c->d_coef_scr,
-                  c->d_J, c->d_coef, c->d_dJdu, c->d_flag, c->d_hist, c->d_stage, c->d_ws, c->d_red, c->d_Bs, c->d_cstage, c->d_fws, c->d_AH, c->d_Cst, c->d_gws, c->d_pws, c->d_ps, c->d_At, c->d_steps, c->d_terms, c->d_src, c->d_rsec, c->d_sink, c->d_blkrec, c->d_xn, c->d_env_ws, c->d_env_p, c->d_env_lam};
-  for (void* p : ptrs)
-    if (p) hipFree(p);
   for (auto& m : c->marks) {
     hipEventDestroy(m.a);
     hipEventDestroy(m.b);
@@ -688,10 +644,7 @@ void qoc_destroy(qoc_ctx* c) {
   }
   for (auto e : c->event_pool) hipEventDestroy(e);
   for (auto e : c->sync_ev) hipEventDestroy(e);
-  if (c->stream2) {
-    hipStreamSynchronize(c->stream2);
-    hipStreamDestroy(c->stream2);
-  }
+  if (c->stream2) hipStreamDestroy(c->stream2);
   if (c->stream) hipStreamDestroy(c->stream);
   delete c;
 }
@@ -726,7 +679,7 @@ int qoc_set_generators(qoc_ctx* c, const double* A0, const double* const* Aj) {
   int r = upload(c, A0, c->d_A, NN);
   for (int j = 0; j < c->nu && r == QOC_OK; ++j) {
     if (!Aj[j]) return fail(c, QOC_ERR_ARG, "A[%d] is null", j);
-    r = upload(c, Aj[j], (char*)c->d_A + (j + 1) * NN * c->esz, NN);
+    r = upload(c, Aj[j], c->d_A.as<char>() + (j + 1) * NN * c->esz, NN);
   }
   if (r != QOC_OK) return r;
   if (c->d_AH) HIPCHK(c, launch_gen_aux(c));
@@ -814,7 +767,7 @@ int qoc_set_generators(qoc_ctx* c, const double* A0, const double* const* Aj) {
       c->tprm.mur[j] = mr;
       c->tprm.mui[j] = mi;
       if (!c->tchain_ok) continue;
-      r = upload(c, sh.data(), (char*)c->d_At + j * NN * c->esz, NN);
+      r = upload(c, sh.data(), c->d_At.as<char>() + j * NN * c->esz, NN);
       if (r == QOC_OK) HIPCHK(c, hipStreamSynchronize(c->stream));  // sh is reused
     }
     if (r != QOC_OK) return r;
@@ -921,41 +874,22 @@ int qoc_set_generator_ensemble(qoc_ctx* c, int E, const double* A0s, const doubl
   const size_t bytes[8] = {tabs.size() * sizeof(double), prm.size() * sizeof(double), (size_t)E * sizeof(double),
                            BE * sizeof(double), BE * 2 * c->m_user * sizeof(cx<double>),
                            BE * c->Nt * c->nu * sizeof(double), pl.om_bytes, pl.gseg_bytes};
-  void* buf[8] = {};
-  size_t total = 0;
+  DevBuf<void> buf[8];  // (a return before the commit frees them)
   for (int i = 0; i < 8; ++i) {
-    if (!bytes[i]) continue;
-    const hipError_t e_ = hipMalloc(&buf[i], bytes[i]);
-    if (e_ != hipSuccess) {
-      for (int q = 0; q < i; ++q)
-        if (buf[q]) hipFree(buf[q]);
+    const hipError_t e_ = buf[i].alloc(bytes[i]);
+    if (e_ != hipSuccess)
       return fail(c, QOC_ERR_HIP, "the ensemble's workspace (%zu bytes): %s", bytes[i], hipGetErrorString(e_));
-    }
-    if (i < 6) total += bytes[i];
   }
   hipError_t e_ = hipMemcpy(buf[0], tabs.data(), bytes[0], hipMemcpyHostToDevice);
   if (e_ == hipSuccess) e_ = hipMemcpy(buf[1], prm.data(), bytes[1], hipMemcpyHostToDevice);
   if (e_ == hipSuccess) e_ = hipMemcpy(buf[2], w.data(), bytes[2], hipMemcpyHostToDevice);
-  if (e_ != hipSuccess) {
-    for (void* p : buf)
-      if (p) hipFree(p);
-    return fail(c, QOC_ERR_HIP, "the ensemble's tables: %s", hipGetErrorString(e_));
-  }
+  if (e_ != hipSuccess) return fail(c, QOC_ERR_HIP, "the ensemble's tables: %s", hipGetErrorString(e_));
   ens_clear(c);
-  c->d_ens_gtab = (double2*)buf[0];
-  c->d_ens_prm = (double*)buf[1];
-  c->d_ens_w = (double*)buf[2];
-  c->d_ens_J = (double*)buf[3];
-  c->d_ens_coef = (cx<double>*)buf[4];
-  c->d_ens_g = (double*)buf[5];
-  c->d_ens_om = (double*)buf[6];
-  c->d_ens_gseg = (double2*)buf[7];
-  c->ens_gseg_bytes = pl.gseg_bytes;
-  c->ens_risk_bytes = pl.om_bytes + pl.gseg_bytes;
+  DevBufBase* dst[8] = {&c->d_ens_gtab, &c->d_ens_prm, &c->d_ens_w, &c->d_ens_J, &c->d_ens_coef, &c->d_ens_g,
+                        &c->d_ens_om, &c->d_ens_gseg};
+  for (int i = 0; i < 8; ++i) dst[i]->adopt(std::move(buf[i]));
   c->ens_route = pl.route;
   c->h_ens_w = w;
-  c->ens_bytes = total;
-  c->dev_bytes += total + c->ens_risk_bytes;
   c->ens_E = E;
   c->fwd.valid = false;  // states are per member from here on
   return QOC_OK;
@@ -981,10 +915,7 @@ int qoc_set_time_scale(qoc_ctx* c, const double* tau) {
   // lazily kept states / co-states are rebuilt with the context as it is (an eval under the scale keeps nothing lazy)
   if (int r0 = blk_materialize(c)) return r0;
   const size_t bytes = (size_t)2 * c->B * sizeof(double);
-  if (!c->d_ts) {
-    HIPCHK(c, hipMalloc((void**)&c->d_ts, bytes));
-    c->dev_bytes += bytes;
-  }
+  if (!c->d_ts) HIPCHK(c, c->d_ts.alloc(bytes));
   // on the context's stream, behind every queued eval that still reads the earlier values
   HIPCHK(c, hipMemcpyAsync(c->d_ts, tau, bytes / 2, hipMemcpyHostToDevice, c->stream));
   HIPCHK(c, hipMemsetAsync(c->d_ts + c->B, 0, bytes / 2, c->stream));
@@ -1040,33 +971,21 @@ int qoc_set_ensemble_objective(qoc_ctx* c, int kind, double param) {
     // with an ensemble set this setter completes the pair: ω, and G (D) at the segment ends where route 2 is taken;
     // the new buffers first, so that a failed allocation leaves the context as it was
     const EnsPlan pl = blkseg_ens_plan(c, c->ens_E, c->h_ens_w.data(), kind, param);
-    void *om = nullptr, *gs = nullptr;
+    DevBuf<void> om, gs;  // (a return before the commit frees them)
     if (pl.om_bytes && !c->d_ens_om) {
-      const hipError_t e_ = hipMalloc(&om, pl.om_bytes);
+      const hipError_t e_ = om.alloc(pl.om_bytes);
       if (e_ != hipSuccess)
         return fail(c, QOC_ERR_HIP, "the objective's workspace (%zu bytes): %s", pl.om_bytes, hipGetErrorString(e_));
     }
-    if (pl.gseg_bytes > c->ens_gseg_bytes) {
-      const hipError_t e_ = hipMalloc(&gs, pl.gseg_bytes);
-      if (e_ != hipSuccess) {
-        if (om) hipFree(om);
+    if (pl.gseg_bytes > c->d_ens_gseg.bytes()) {
+      const hipError_t e_ = gs.alloc(pl.gseg_bytes);
+      if (e_ != hipSuccess)
         return fail(c, QOC_ERR_HIP, "the objective's workspace (%zu bytes): %s", pl.gseg_bytes, hipGetErrorString(e_));
-      }
     }
-    if (om) {
-      c->d_ens_om = (double*)om;
-      c->ens_risk_bytes += pl.om_bytes;
-      c->dev_bytes += pl.om_bytes;
-    }
+    if (om) c->d_ens_om.adopt(std::move(om));
     if (gs) {
-      if (c->d_ens_gseg) {
-        if (c->stream) hipStreamSynchronize(c->stream);  // a queued eval may still read it
-        hipFree(c->d_ens_gseg);
-      }
-      c->d_ens_gseg = (double2*)gs;
-      c->ens_risk_bytes += pl.gseg_bytes - c->ens_gseg_bytes;
-      c->dev_bytes += pl.gseg_bytes - c->ens_gseg_bytes;
-      c->ens_gseg_bytes = pl.gseg_bytes;
+      if (c->d_ens_gseg && c->stream) hipStreamSynchronize(c->stream);  // a queued eval may still read it
+      c->d_ens_gseg.adopt(std::move(gs));
     }
     route = pl.route;
   }
@@ -1189,10 +1108,7 @@ int qoc_set_costate_source(qoc_ctx* c, const double* dLdx) {
     return QOC_OK;
   }
   const size_t cnt = (size_t)c->B * (c->Nt + 1), n = cnt * c->N * c->m_user;  // allocated for m_user >= m
-  if (!c->d_src) {
-    HIPCHK(c, hipMalloc(&c->d_src, n * c->esz));
-    c->dev_bytes += n * c->esz;
-  }
+  if (!c->d_src) HIPCHK(c, c->d_src.alloc(n * c->esz));
   int r = upload_states(c, dLdx, c->d_src, cnt, nullptr);
   if (r) return r;
   HIPCHK(c, hipStreamSynchronize(c->stream));
@@ -1293,8 +1209,7 @@ int qoc_set_compression(qoc_ctx* c, const int* rows1, int nr1, const int* cols1,
   c->grad_rr = c->grad_rr_any_m && grad_rr_cols(c->m);
   if (c->grad_rr && !c->d_gws) {  // the fused gradient's W0/W1 workspace (qoc_create sized none for m_user)
     const size_t bytes = 2 * (size_t)N * c->B * (c->Nt + 1) * mu_ * c->esz;
-    HIPCHK(c, hipMalloc(&c->d_gws, bytes));
-    c->dev_bytes += bytes;
+    HIPCHK(c, c->d_gws.alloc(bytes));
   }
   c->fwd.valid = false;
   return QOC_OK;
@@ -1439,7 +1354,7 @@ int qoc_grape_sensitivity(qoc_ctx* c, const double* u, int order, const double* 
     // λ_{Nt+1} for every seed lives at Lam[b][Nt]
     const size_t Nm = (size_t)c->N * c->m, Nmu = (size_t)c->N * c->m_user;
     for (int b = 0; b < c->B; ++b) {
-      r = upload_states(c, lambda_final + 2 * Nmu * b, (char*)c->d_L + ((size_t)b * (c->Nt + 1) + c->Nt) * Nm * c->esz,
+      r = upload_states(c, lambda_final + 2 * Nmu * b, c->d_L.as<char>() + ((size_t)b * (c->Nt + 1) + c->Nt) * Nm * c->esz,
                         1, nullptr);
       if (r) return r;
     }
@@ -1463,7 +1378,7 @@ int qoc_get_states(qoc_ctx* c, int seed, int k, double* x_out) {
     if (r) return r;
   }
   const size_t Nm = (size_t)c->N * c->m;
-  return download_states(c, (char*)c->d_X + ((size_t)seed * (c->Nt + 1) + k) * Nm * c->esz, x_out);
+  return download_states(c, c->d_X.as<char>() + ((size_t)seed * (c->Nt + 1) + k) * Nm * c->esz, x_out);
 }
 
 int qoc_get_costates(qoc_ctx* c, int seed, int k, double* lam_out) {
@@ -1472,7 +1387,7 @@ int qoc_get_costates(qoc_ctx* c, int seed, int k, double* lam_out) {
   if (seed < 0 || seed >= c->B || k < 0 || k > c->Nt) return fail(c, QOC_ERR_ARG, "index out of range");
   HIPCHK(c, hipSetDevice(c->dev));
   const size_t Nm = (size_t)c->N * c->m;
-  const void* src = (char*)c->d_L + ((size_t)seed * (c->Nt + 1) + k) * Nm * c->esz;
+  const void* src = c->d_L.as<char>() + ((size_t)seed * (c->Nt + 1) + k) * Nm * c->esz;
   if (c->bwd.lazy) {
     const int r = blku_costates(c);
     if (r) return r;
@@ -1510,11 +1425,11 @@ int qoc_get_propagator(qoc_ctx* c, int seed, int k, double* U_out) {
   const size_t NN = (size_t)c->N * c->N, unit = (size_t)seed * c->Nt + k;
   if (c->chain_mode == 1) {  // the Taylor-action chains form no propagators: exp(A_k) of this slice on demand
     hipError_t e = launch_expm(c->prec, c->stream, c->N, c->nu, 1, c->d_A, c->d_u + unit * c->nu, nullptr,
-                               (char*)c->d_U + unit * NN * c->esz, nullptr, nullptr, nullptr, c->expm_run,
+                               c->d_U.as<char>() + unit * NN * c->esz, nullptr, nullptr, nullptr, c->expm_run,
                                c->d_hist + 5 * 64, c->d_ps, c->a0norm > 4.0 * kTheta12);
     if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "k_expm (propagator on demand): %s", hipGetErrorString(e));
   }
-  return download(c, (char*)c->d_U + unit * NN * c->esz, U_out, NN);
+  return download(c, c->d_U.as<char>() + unit * NN * c->esz, U_out, NN);
 }
 
 int qoc_set_profiling(qoc_ctx* c, int enable) {
@@ -1576,12 +1491,9 @@ int qoc_set_spline_basis(qoc_ctx* c, const double* Bs, int ns) {
   if (ns < 1) return fail(c, QOC_ERR_ARG, "nsplines must be >= 1 (got %d)", ns);
   HIPCHK(c, hipSetDevice(c->dev));
   HIPCHK(c, hipStreamSynchronize(c->stream));  // queued spline kernels may still read the old basis
-  if (c->d_Bs) HIPCHK(c, hipFree(c->d_Bs));
-  if (c->d_cstage) HIPCHK(c, hipFree(c->d_cstage));
-  c->d_Bs = nullptr;
-  c->d_cstage = nullptr;
-  HIPCHK(c, hipMalloc((void**)&c->d_Bs, (size_t)c->Nt * ns * sizeof(double)));
-  HIPCHK(c, hipMalloc((void**)&c->d_cstage, (size_t)2 * c->B * ns * c->nu * sizeof(double)));
+  c->d_cstage.release();
+  HIPCHK(c, c->d_Bs.alloc((size_t)c->Nt * ns * sizeof(double)));
+  HIPCHK(c, c->d_cstage.alloc((size_t)2 * c->B * ns * c->nu * sizeof(double)));
   HIPCHK(c, hipMemcpy(c->d_Bs, Bs, (size_t)c->Nt * ns * sizeof(double), hipMemcpyHostToDevice));
   c->ns = ns;
   // states and co-states of a spline propagate belong to the old basis' u: qoc_sensitivity_spline must now see
@@ -1727,8 +1639,8 @@ int qoc_propagate_envelope(qoc_ctx* c, int kind, const double* params, int np, d
   const long long nsteps = (long long)std::llround(tgate / dt);
   const size_t env_lds = (size_t)(c->nu + 1) * c->N * c->N * c->esz;
   if (env_lds > 160 * 1024) return fail(c, QOC_ERR_UNSUPPORTED, "generators (%zu B) exceed the 160 KiB LDS", env_lds);
-  double* dP = nullptr;
-  HIPCHK(c, hipMalloc((void**)&dP, (size_t)c->B * np * sizeof(double)));
+  DevBuf<double> dP;
+  HIPCHK(c, dP.alloc((size_t)c->B * np * sizeof(double)));
   hipError_t e = hipMemcpy(dP, params, (size_t)c->B * np * sizeof(double), hipMemcpyHostToDevice);
   forward_begin(c);  // J and x(tgate) are rewritten below; states other than x(tgate) are not stored: fwd stays invalid
   if (e == hipSuccess) e = launch_envelope(c, kind, dP, np, dt, nsteps);
@@ -1736,11 +1648,11 @@ int qoc_propagate_envelope(qoc_ctx* c, int kind, const double* params, int np, d
   if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
   if (e == hipSuccess && J_out && c->cost_kind != QOC_COST_EXTERNAL)
     e = hipMemcpy(J_out, c->d_J, c->B * sizeof(double), hipMemcpyDeviceToHost);
-  hipFree(dP);
+  dP.release();
   if (e == hipSuccess && x_out) {
     const size_t Nm = (size_t)c->N * c->m, Nmu = (size_t)c->N * c->m_user;
     for (int b = 0; b < c->B; ++b) {
-      int r2 = download_states(c, (char*)c->d_X + ((size_t)b * (c->Nt + 1) + c->Nt) * Nm * c->esz, x_out + 2 * Nmu * b);
+      int r2 = download_states(c, c->d_X.as<char>() + ((size_t)b * (c->Nt + 1) + c->Nt) * Nm * c->esz, x_out + 2 * Nmu * b);
       if (r2) return r2;
     }
   }
@@ -1809,8 +1721,8 @@ int qoc_eval_envelope(qoc_ctx* c, int kind, const double* params, int np, double
   EnvGradPlan pl;
   if ((r = env_grad_plan(c, nsteps, &pl))) return r;
   const size_t Nm = (size_t)c->N * c->m;
-  if (!c->d_env_p) HIPCHK(c, hipMalloc((void**)&c->d_env_p, (size_t)c->B * 128 * sizeof(double)));
-  if (ext && !c->d_env_lam) HIPCHK(c, hipMalloc(&c->d_env_lam, (size_t)c->B * Nm * c->esz));
+  if (!c->d_env_p) HIPCHK(c, c->d_env_p.alloc((size_t)c->B * 128 * sizeof(double)));
+  if (ext && !c->d_env_lam) HIPCHK(c, c->d_env_lam.alloc((size_t)c->B * Nm * c->esz));
   double* dP = c->d_env_p;
   double* dG = c->d_env_p + (size_t)c->B * 64;
   HIPCHK(c, hipMemcpyAsync(dP, params, (size_t)c->B * np * sizeof(double), hipMemcpyHostToDevice, c->stream));
@@ -1821,7 +1733,7 @@ int qoc_eval_envelope(qoc_ctx* c, int kind, const double* params, int np, double
   HIPCHK(c, hipStreamSynchronize(c->stream));
   if (x_out) {
     for (int b = 0; b < c->B; ++b) {
-      r = download_states(c, (char*)c->d_X + ((size_t)b * (c->Nt + 1) + c->Nt) * Nm * c->esz, x_out + 2 * Nm * b);
+      r = download_states(c, c->d_X.as<char>() + ((size_t)b * (c->Nt + 1) + c->Nt) * Nm * c->esz, x_out + 2 * Nm * b);
       if (r) return r;
     }
   }
@@ -1839,7 +1751,7 @@ int qoc_get_info(qoc_ctx* c, long long* info) {
   info[0] = c->big ? 1 : 0;
   info[1] = c->chunk;
   info[2] = c->ns_iters;
-  info[3] = (long long)c->dev_bytes;
+  info[3] = (long long)c->mem.bytes;
   info[4] = c->chain_mode;
   info[5] = c->big ? c->expm_alg : c->expm_run;  // the large-N pipeline keeps its own (Taylor / Padé) choice
   info[6] = c->chain_mode == 1 && c->cheb && tchain_mf(c) ? 1 : 0;  // Taylor-action chains: Chebyshev terms
@@ -1893,32 +1805,26 @@ int qoc_comm_init(qoc_ctx* c, int world, int rank, const void* id, long long see
     r.commDestroy(c->comm);
     c->comm = nullptr;
   }
-  if (c->d_best) HIPCHK(c, hipFree(c->d_best));
-  c->d_best = nullptr;
+  c->d_best.release();
   c->jbest = {};  // the gathered slot goes with the buffer
   c->world = 1;
   c->rank = 0;
   c->seed_offset = 0;
-  double* best = nullptr;
-  HIPCHK(c, hipMalloc((void**)&best, (size_t)(4 + 2 * world) * sizeof(double)));
+  DevBuf<double> best;
+  HIPCHK(c, best.alloc((size_t)(4 + 2 * world) * sizeof(double)));
   // With a unique id a real RCCL communicator is created, also for world = 1 (a one-rank all-gather through the
   // same code path as the multi-GPU run); without one (world = 1 only) the context covers its own seeds.
   ncclComm_t comm = nullptr;
   if (id) {
-    if (!r.ok) {
-      hipFree(best);
-      return fail(c, QOC_ERR_UNSUPPORTED, "RCCL (librccl.so.1) not available");
-    }
+    if (!r.ok) return fail(c, QOC_ERR_UNSUPPORTED, "RCCL (librccl.so.1) not available");
     ncclUniqueId uid;
     std::memcpy(&uid, id, sizeof(uid));
     const ncclResult_t e = r.commInitRank(&comm, world, uid, rank);
-    if (e != ncclSuccess || !comm) {
-      hipFree(best);
+    if (e != ncclSuccess || !comm)
       return fail(c, QOC_ERR_HIP, "ncclCommInitRank (rank %d of %d): %s", rank, world, r.getErrorString(e));
-    }
   }
   c->comm = comm;
-  c->d_best = best;
+  c->d_best.adopt(std::move(best));
   c->world = world;
   c->rank = rank;
   c->seed_offset = seed_offset;
@@ -1934,7 +1840,7 @@ int qoc_allgather_best_dev(qoc_ctx* c, double* d_out) {
   if (!c) return fail(nullptr, QOC_ERR_ARG, "null context");
   HIPCHK(c, hipSetDevice(c->dev));
   if (!c->d_best) {  // no communicator: this context alone (world 1, seed offset 0)
-    HIPCHK(c, hipMalloc((void**)&c->d_best, 6 * sizeof(double)));
+    HIPCHK(c, c->d_best.alloc(6 * sizeof(double)));
     c->world = 1;
     c->rank = 0;
   }
@@ -2060,13 +1966,13 @@ int qoc_expm_batched(int device, int N, int count, int precision, const double* 
   HIPCHK(c, hipSetDevice(device));
   HIPCHK(c, hipStreamCreateWithFlags(&c->stream, hipStreamNonBlocking));
   const size_t n = (size_t)count * N * N;
-  void *dA = nullptr, *dX = nullptr;
-  int *dd = nullptr, *ds = nullptr;
+  DevBuf<void> dA, dX;
+  DevBuf<int> dd, ds;
   int r = QOC_OK;
-  hipError_t e = hipMalloc(&dA, n * c->esz);
-  if (e == hipSuccess) e = hipMalloc(&dX, n * c->esz);
-  if (e == hipSuccess) e = hipMalloc(&dd, count * sizeof(int));
-  if (e == hipSuccess) e = hipMalloc(&ds, count * sizeof(int));
+  hipError_t e = dA.alloc(n * c->esz);
+  if (e == hipSuccess) e = dX.alloc(n * c->esz);
+  if (e == hipSuccess) e = dd.alloc(count * sizeof(int));
+  if (e == hipSuccess) e = ds.alloc(count * sizeof(int));
   if (e != hipSuccess) r = fail(nullptr, QOC_ERR_HIP, "hipMalloc: %s", hipGetErrorString(e));
   if (!r) r = upload(c, A, dA, n);
   if (!r) {
@@ -2076,12 +1982,7 @@ int qoc_expm_batched(int device, int N, int count, int precision, const double* 
   if (!r) r = download(c, dX, X, n);
   if (!r && degree_out) hipMemcpy(degree_out, dd, count * sizeof(int), hipMemcpyDeviceToHost);
   if (!r && squarings_out) hipMemcpy(squarings_out, ds, count * sizeof(int), hipMemcpyDeviceToHost);
-  hipFree(dA);
-  hipFree(dX);
-  hipFree(dd);
-  hipFree(ds);
-  if (c->d_stage) hipFree(c->d_stage);
-  c->d_stage = nullptr;
+  c->d_stage.release();  // (before its stream goes; the locals at scope exit)
   hipStreamDestroy(c->stream);
   c->stream = nullptr;
   if (r) g_err = tmp.err.empty() ? g_err : tmp.err;
@@ -2095,24 +1996,24 @@ int qoc_expm_jacobian(int device, int N, int nu, const double* A0, const double*
   if (hipSetDevice(device) != hipSuccess) return fail(nullptr, QOC_ERR_HIP, "hipSetDevice");
   const size_t NN = (size_t)N * N, bytes = NN * 16;
   // buffers: A0, Aj[nu], X, AjX, XAj, X2, out[nu]
-  std::vector<void*> bufs(2 * nu + 5, nullptr);
+  std::vector<DevBuf<void>> bufs(2 * nu + 5);
   for (auto& b : bufs)
-    if (hipMalloc(&b, bytes) != hipSuccess) return fail(nullptr, QOC_ERR_HIP, "hipMalloc");
-  auto A0d = (cx<double>*)bufs[0];
-  auto Xd = (cx<double>*)bufs[nu + 1];
-  auto AjXd = (cx<double>*)bufs[nu + 2];
-  auto XAjd = (cx<double>*)bufs[nu + 3];
-  auto X2d = (cx<double>*)bufs[nu + 4];
+    if (b.alloc(bytes) != hipSuccess) return fail(nullptr, QOC_ERR_HIP, "hipMalloc");
+  auto A0d = bufs[0].as<cx<double>>();
+  auto Xd = bufs[nu + 1].as<cx<double>>();
+  auto AjXd = bufs[nu + 2].as<cx<double>>();
+  auto XAjd = bufs[nu + 3].as<cx<double>>();
+  auto X2d = bufs[nu + 4].as<cx<double>>();
   hipMemcpy(A0d, A0, bytes, hipMemcpyHostToDevice);
   for (int j = 0; j < nu; ++j) hipMemcpy(bufs[1 + j], Aj[j], bytes, hipMemcpyHostToDevice);
   const dim3 g((unsigned)((NN + 255) / 256)), t(256);
   // X = A0 + sum p_j A_j   (src/gradient_computations.jl:188-191)
   hipLaunchKernelGGL(k_axpby, g, t, 0, 0, (int)NN, Xd, 1.0, A0d, 0.0, (const cx<double>*)nullptr);
   for (int j = 0; j < nu; ++j)
-    hipLaunchKernelGGL(k_axpby, g, t, 0, 0, (int)NN, Xd, 1.0, Xd, p[j], (const cx<double>*)bufs[1 + j]);
+    hipLaunchKernelGGL(k_axpby, g, t, 0, 0, (int)NN, Xd, 1.0, Xd, p[j], bufs[1 + j].as<const cx<double>>());
   for (int j = 0; j < nu; ++j) {
-    auto Aj_d = (const cx<double>*)bufs[1 + j];
-    auto out = (cx<double>*)bufs[nu + 5 + j];
+    auto Aj_d = bufs[1 + j].as<const cx<double>>();
+    auto out = bufs[nu + 5 + j].as<cx<double>>();
     hipLaunchKernelGGL(k_axpby, g, t, 0, 0, (int)NN, out, dt, Aj_d, 0.0, (const cx<double>*)nullptr);  // :179-181
     if (order >= 2) {  // :194-197
       hipLaunchKernelGGL(k_cgemm_naive, g, t, 0, 0, N, Aj_d, (const cx<double>*)Xd, AjXd, 1.0, 0.0);
@@ -2138,7 +2039,6 @@ int qoc_expm_jacobian(int device, int N, int nu, const double* A0, const double*
   int r = QOC_OK;
   if (hipDeviceSynchronize() != hipSuccess) r = fail(nullptr, QOC_ERR_HIP, "expm_jacobian kernels failed");
   for (int j = 0; j < nu && !r; ++j) hipMemcpy(dFdp_out + 2 * NN * j, bufs[nu + 5 + j], bytes, hipMemcpyDeviceToHost);
-  for (auto b : bufs) hipFree(b);
   return r;
 }
 

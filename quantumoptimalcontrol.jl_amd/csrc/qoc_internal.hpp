@@ -32,6 +32,7 @@
 #include "../../include/qoc.h"
 #include "qoc_chain.hpp"
 #include "qoc_comm.hpp"
+#include "qoc_devbuf.hpp"
 #include "qoc_tchain.hpp"
 
 namespace qoc {
@@ -111,33 +112,36 @@ struct qoc_ctx {
   double bwd_last_frac = 0.5;           // last range's length relative to the others
   int bwd_prio = 0;                     // bit 0: s_setprio in the chain; bit 1: low-priority gradient stream
   int bwd_prestate = 2;                 // P1, P2 of every slice beside the first backward range (k_grad_rr_s): 0 off, 1 on, 2 auto
-  void* d_A = nullptr;    // (nu+1) x N*N
-  void* d_x0 = nullptr;   // N*m or B*N*m
+  // Every device allocation of the context is a DevBuf (qoc_devbuf.hpp) that reports to mem; mem.bytes is info[3] of
+  // qoc_get_info.  Whether a buffer is counted is said here, at its declaration, and nowhere else.  kUncounted without
+  // a remark: as before (it never was counted; DESIGN.md lists them); d_env_ws has a reason of its own.
+  DevLedger mem;
+  DevBuf<void> d_A{mem, kCounted};    // (nu+1) x N*N
+  DevBuf<void> d_x0{mem, kCounted};   // N*m or B*N*m
   int x0_per_seed = 0;
-  void* d_Xt = nullptr;   // N*m target
+  DevBuf<void> d_Xt{mem, kCounted};   // N*m target
   int cost_kind = QOC_COST_TRACE;
   double cost_n = 1.0;
-  unsigned char* d_pmask = nullptr;
+  DevBuf<unsigned char> d_pmask{mem, kCounted};
   double mu = 0.0;
-  void* d_src = nullptr;   // B x (Nt+1) x N x m caller's dL/dx(x_k) (qoc_set_costate_source), device precision
+  DevBuf<void> d_src{mem, kCounted};   // B x (Nt+1) x N x m caller's dL/dx(x_k) (qoc_set_costate_source), device precision
   bool src_on = false;
-  double* d_u = nullptr;     // B*nu*Nt, u of the last propagate
-  void* d_U = nullptr;       // B*Nt*N*N
-  void* d_X = nullptr;       // B*(Nt+1)*N*m
-  void* d_L = nullptr;       // B*(Nt+1)*N*m
-  double* d_J = nullptr;     // B
-  cx<double>* d_coef = nullptr;  // B*m
-  double* d_dJdu = nullptr;  // B*nu*Nt
-  int* d_flag = nullptr;
-  double* d_sink = nullptr;  // TCHAIN_SINK doubles: the MFMA chains' branch-free stores of lanes without an element
-  unsigned long long* d_hist = nullptr;  // 5*64 reference (Padé) selection + 8*64 executed Taylor (r, s) / T12 s
+  DevBuf<double> d_u{mem, kCounted};     // B*nu*Nt, u of the last propagate
+  DevBuf<void> d_U{mem, kCounted};       // B*Nt*N*N
+  DevBuf<void> d_X{mem, kCounted};       // B*(Nt+1)*N*m
+  DevBuf<void> d_L{mem, kCounted};       // B*(Nt+1)*N*m
+  DevBuf<double> d_J{mem, kCounted};     // B
+  DevBuf<cx<double>> d_coef{mem, kCounted};  // B*m
+  DevBuf<double> d_dJdu{mem, kCounted};  // B*nu*Nt
+  DevBuf<int> d_flag{mem, kCounted};
+  DevBuf<double> d_sink{mem, kCounted};  // TCHAIN_SINK doubles: the MFMA chains' branch-free stores of lanes without an element
+  DevBuf<unsigned long long> d_hist{mem, kCounted};  // 5*64 reference (Padé) selection + 8*64 executed Taylor (r, s) / T12 s
   int chain_cb_fwd = 0, chain_cb_bwd = 0;  // 0: chain_shape's column block; QOC_CHAIN_CB_FWD / _BWD = 1 | 2 (N > 32)
   int expm_alg = 1;  // 1 Taylor: register-resident T12 (default), 2 LDS Paterson-Stockmeyer (QOC_EXPM_LDS=1), 0 Padé (QOC_EXPM_PADE=1)
   int prop_method = 0;                   // QOC_PROP_EXPM / QOC_PROP_TSIT5
   int nsub = 10;                         // Tsit5 steps per slice (reference dt = 0.1 Δt)
   int ode_kernel = 0;                    // 0 register-resident rows when N fits, 1 LDS rows (QOC_ODE_LDS=1)
-  double* d_stage = nullptr;             // host->device staging (fp64 complex), max(B*N*m, (nu+1)*N*N)*2
-  size_t stage_elems = 0;
+  DevBuf<double> d_stage{mem, kUncounted};             // host->device staging (fp64 complex), max(B*N*m, (nu+1)*N*N)*2
   std::vector<double> h_u;
   std::vector<double> h_coef;  // spline coefficients of the last qoc_propagate_spline
   // live per-kernel timing (hipEvents recorded on `stream` around each hot-path launch)
@@ -161,8 +165,8 @@ struct qoc_ctx {
   // large-N path (N beyond the LDS-resident kernels): chunked batched-GEMM pipeline
   bool big = false;
   int chunk = 0;                // slices per chunk
-  void* d_ws = nullptr;         // chunk workspace
-  double* d_red = nullptr;      // per-item reductions (chunk + 8 doubles)
+  DevBuf<void> d_ws{mem, kCounted};         // chunk workspace
+  DevBuf<double> d_red{mem, kCounted};      // per-item reductions (chunk + 8 doubles)
   long long big_hist[5 * 64] = {};
   long long big_thist[9 * 64] = {};  // executed Taylor (r, s) on the large-N path; row 8: T8
   long long ns_iters = 0;       // Newton-Schulz iterations executed (all chunks)
@@ -170,21 +174,19 @@ struct qoc_ctx {
   // chunk's Taylor degree / squarings then follow the 2-norm bound Σ_j |c_jk| ρ_j instead of the 1-norm
   double big_rho[9] = {};
   bool big_rho_ok = false;
-  size_t dev_bytes = 0;
   // spline parameterisation (examples/ipopt_callbacks_exp.jl:13-14, 28)
-  double* d_Bs = nullptr;  // Nt x ns
+  DevBuf<double> d_Bs{mem, kUncounted};  // Nt x ns
   int ns = 0;
-  double* d_cstage = nullptr;  // host-pointer variants: B x ns x nu coefficients / gradient
+  DevBuf<double> d_cstage{mem, kUncounted};  // host-pointer variants: B x ns x nu coefficients / gradient
   // GEMM-shaped gradient of the LDS-resident path (order 3, N >= 32: below that the 64-row GEMM tiles
   // are mostly padding and the per-slice k_grad is faster): generator layouts + P/Q/W workspace
-  void* d_AH = nullptr;    // (nu+1) x N*N: [A0^H | A1^H | ...]
-  void* d_Cst = nullptr;   // nu N x N: [A1; A2; ...]
-  void* d_gws = nullptr;   // 6 x N x B(Nt+1)m
-  void* d_pws = nullptr;   // 2 x N x B(Nt+1)m: P1, P2 of the state-side gradient pass (bwd_prestate)
-  size_t pws_bytes = 0;
+  DevBuf<void> d_AH{mem, kCounted};    // (nu+1) x N*N: [A0^H | A1^H | ...]
+  DevBuf<void> d_Cst{mem, kCounted};   // nu N x N: [A1; A2; ...]
+  DevBuf<void> d_gws{mem, kCounted};   // 6 x N x B(Nt+1)m
+  DevBuf<void> d_pws{mem, kCounted};   // 2 x N x B(Nt+1)m: P1, P2 of the state-side gradient pass (bwd_prestate)
   bool grad_gemm = true;
   bool grad_rr = false;  // fused register-resident order-3 gradient (qoc_grad_rr.hpp)
-  int* d_ps = nullptr;   // k_expm_rr pass-2 counter + list of Paterson-Stockmeyer units
+  DevBuf<int> d_ps{mem, kCounted};   // k_expm_rr pass-2 counter + list of Paterson-Stockmeyer units
   double a0norm = 0.0;   // ||A0||_1 of the generators (host-side, at qoc_set_generators)
   // exponential that runs: expm_alg, except that when every slice has a large norm (||A0||_1 > 4 theta_12,
   // tunable bus: ||A_k||_1 ~ 30) the default register-resident Taylor hands over to the reference's own Padé-13
@@ -198,13 +200,13 @@ struct qoc_ctx {
   int chain_mode = 0;            // 0: propagators (k_expm + k_chain_*), 1: Taylor action (k_tchain_*)
   int chain_req = QOC_CHAIN_AUTO;  // what qoc_set_chain asked for (kept across qoc_set_generators)
   bool tchain_ok = false;        // the shape fits the Taylor-action kernels
-  void* d_At = nullptr;          // (nu+1) N x N shifted generators Ã_j = A_j - μ_j I
-  TStep* d_steps = nullptr;      // B x Nt (P, s, e^{μ_k})
-  unsigned long long* d_terms = nullptr;  // Σ P s per forward (executed Taylor terms per direction)
+  DevBuf<void> d_At{mem, kCounted};          // (nu+1) N x N shifted generators Ã_j = A_j - μ_j I
+  DevBuf<TStep> d_steps{mem, kCounted};      // B x Nt (P, s, e^{μ_k})
+  DevBuf<unsigned long long> d_terms{mem, kCounted};  // Σ P s per forward (executed Taylor terms per direction)
   TChainParams tprm{};
   bool cheb_ok = false;          // generators skew-Hermitian with imaginary shifts: Chebyshev applies
   bool cheb = false;             // Chebyshev terms (k_tchain_prep_cheb) instead of Taylor (QOC_TCHAIN_POLY=taylor)
-  double* d_tcoef = nullptr;     // B x Nt x TCHEB_STRIDE Chebyshev coefficients (allocated on first use)
+  DevBuf<double> d_tcoef{mem, kCounted};     // B x Nt x TCHEB_STRIDE Chebyshev coefficients (allocated on first use)
   long long props_since_reset = 0;  // forward passes since the last Padé-histogram reset (chain mode 1)
   // Captured products (register-resident MFMA chains, order-3 fused gradient): the chains write their first two
   // products per slice (forward -> d_pws, backward -> d_gws) and the gradient is k_grad_rr_c, contractions only.
@@ -216,13 +218,12 @@ struct qoc_ctx {
   // the MFMA chains with the state in registers (TChainRot): 1 (default) for N <= 32 with nu <= 2, 3 also for
   // N <= 48 (generators in LDS), 0 off: TChainMF everywhere (QOC_TCHAIN_ROT)
   int tchain_rot = 1;
-  double* d_u_lam = nullptr;     // B x Nt x nu: u of the backward that left λ_k to be rebuilt (bwd.lazy)
-  void* d_blkU = nullptr;        // B x Nt x NB^2 x nblk complex: block propagators of the eval's forward (fused backward)
-  size_t blkU_bytes = 0;         // its allocated size (reallocated when a new block layout needs more)
+  DevBuf<double> d_u_lam{mem, kCounted};     // B x Nt x nu: u of the backward that left λ_k to be rebuilt (bwd.lazy)
+  DevBuf<void> d_blkU{mem, kCounted};        // B x Nt x NB^2 x nblk complex: block propagators of the eval's forward (fused backward;
+                                             // reallocated when a new block layout needs more)
   // one control: the propagators interpolated in u (qoc_blkp.hpp k_blkp_int): the coefficient matrices of the control
   // range [int_lo, int_hi] for the live-wave layout int_wrow, degree int_D (int_ok: valid for the current generators)
-  double2* d_blkp_M = nullptr;
-  size_t blkp_M_bytes = 0;
+  DevBuf<double2> d_blkp_M{mem, kUncounted};
   bool int_ok = false;
   int int_D = 0;
   std::vector<int> int_Db;           // per live wave block
@@ -238,15 +239,13 @@ struct qoc_ctx {
   size_t int_noff = 0, int_nsoff = 0;
   bool int_failed = false;           // [int_fail_lo, int_fail_hi] did not converge (a wider range will not either)
   double int_fail_lo = 0.0, int_fail_hi = 0.0;
-  double* d_minmax = nullptr;        // k_minmax partials (256 blocks x 2)
-  double* h_minmax = nullptr;        // pinned host copy
-  double2* d_blkp_ph = nullptr;      // B x Nt: e^{μ(u_k)} for the interpolating chains (k_blkp_phase)
-  size_t blkp_ph_n = 0;
-  double* d_blkp_ctab = nullptr; // the Chebyshev form's coefficient table (qoc_blkp.hpp blkp_cheb), for ctab_cm / ctab_rmax
+  DevBuf<double> d_minmax{mem, kUncounted};        // k_minmax partials (256 blocks x 2)
+  DevBuf<double> h_minmax{mem, kUncounted, hipHostMallocDefault};  // pinned host copy
+  DevBuf<double2> d_blkp_ph{mem, kUncounted};      // B x Nt: e^{μ(u_k)} for the interpolating chains (k_blkp_phase)
+  DevBuf<double> d_blkp_ctab{mem, kUncounted}; // the Chebyshev form's coefficient table (qoc_blkp.hpp blkp_cheb), for ctab_cm / ctab_rmax
   int ctab_cm = 0;
   double ctab_rmax = 0.0;
-  double2* d_gseg = nullptr;         // B x NB^2 x S x nblk complex: the segmented forward's G at every segment end (fwd.kind 1)
-  size_t gseg_bytes = 0;
+  DevBuf<double2> d_gseg{mem, kCounted};         // B x NB^2 x S x nblk complex: the segmented forward's G at every segment end (fwd.kind 1)
   // the segmented eval's launch shape, kept between evals: valid while the sizes it was derived from (seg_key: B, Nt,
   // N, m, nu, block rows, blocks, penalised or not, ensemble members) are the context's; the QOC_BLKSEG_W / _S / _RB switches are read
   // when it is derived.  seg_attr[NB - 2][order - 1, exact: 4][mode][penalised]: this context has raised that k_blkseg_eval
@@ -263,99 +262,93 @@ struct qoc_ctx {
   std::vector<int> h_brow;           // nblk x blk_nb rows of each block (-1 padding), the host's copy of d_brow
   // A generator ensemble (qoc_set_generator_ensemble): ens_E > 0 sets evaluated for every pulse, one workgroup of the
   // segmented eval per (pulse, member) and k_ens_reduce behind it (qoc_blkseg.hpp).  The block layout stays the
-  // nominal set's.  Everything below is allocated by the setter, counted in dev_bytes (ens_bytes) and freed when the
+  // nominal set's.  Everything below is allocated by the setter, counted in info[3] and freed when the
   // ensemble is cleared (E = 0, qoc_set_generators) and at qoc_destroy.
   int ens_E = 0;
-  double2* d_ens_gtab = nullptr;     // [E][nblk][3][blk_nb^2]: the members' shifted generator blocks (blk_gen_table)
-  double* d_ens_prm = nullptr;       // E x 9: rad[3] | mur[3] | mui[3] of each member (gen_shift_bounds)
-  double* d_ens_w = nullptr;         // E weights, as given
-  double* d_ens_J = nullptr;         // B x E member costs of the last ensemble eval (qoc_member_costs_dev)
-  cx<double>* d_ens_coef = nullptr;  // B x E x 2m λ_N coefficients
-  double* d_ens_g = nullptr;         // B x E x Nt x nu member gradients
-  size_t ens_bytes = 0;
+  DevBuf<double2> d_ens_gtab{mem, kCounted};     // [E][nblk][3][blk_nb^2]: the members' shifted generator blocks (blk_gen_table)
+  DevBuf<double> d_ens_prm{mem, kCounted};       // E x 9: rad[3] | mur[3] | mui[3] of each member (gen_shift_bounds)
+  DevBuf<double> d_ens_w{mem, kCounted};         // E weights, as given
+  DevBuf<double> d_ens_J{mem, kCounted};         // B x E member costs of the last ensemble eval (qoc_member_costs_dev)
+  DevBuf<cx<double>> d_ens_coef{mem, kCounted};  // B x E x 2m λ_N coefficients
+  DevBuf<double> d_ens_g{mem, kCounted};         // B x E x Nt x nu member gradients
   bool ens_costs = false;            // d_ens_J holds an eval's costs
   // The ensemble's objective (qoc_set_ensemble_objective): a setting of the context that outlives the ensemble.
   // Under a non-mean objective an ensemble eval forms per-pulse member weights ω (k_ens_weights) and takes one of two
   // routes: 1 = the fused launch for every (pulse, member), 2 = the forward half for all, the backward half where ω
   // is not 0.  ens_route is derived by blkseg_ens_plan from the objective, the weights and QOC_ENS_SKIP whenever one of
   // the two setters completes the pair (ensemble + non-mean objective); that setter also allocates ω and, for route 2,
-  // G (and D) at the segment ends per (pulse, member).  Counted in dev_bytes (ens_risk_bytes), freed with the ensemble.
+  // G (and D) at the segment ends per (pulse, member).  Counted in info[3], freed with the ensemble.
   int ens_obj = 0;                   // QOC_ENS_MEAN / _MAX / _CVAR / _LSE
   double ens_obj_param = 0.0;        // α (CVaR) or β (LSE), else 0
   int ens_route = 1;                 // the route the next eval under a non-mean objective takes
   int ens_last_route = 0;            // the last ensemble eval's: 0 = none since a setter, 1 = fused, 2 = forward + active backward
   std::vector<double> h_ens_w;       // the weights, host copy
-  double* d_ens_om = nullptr;        // B x E member weights ω of the last eval under a non-mean objective
-  double2* d_ens_gseg = nullptr;     // B E x NB^2 x S x nblk complex G at the segment ends, and D behind it when penalised
-  size_t ens_gseg_bytes = 0, ens_risk_bytes = 0;
+  DevBuf<double> d_ens_om{mem, kCounted};        // B x E member weights ω of the last eval under a non-mean objective
+  DevBuf<double2> d_ens_gseg{mem, kCounted};     // B E x NB^2 x S x nblk complex G at the segment ends, and D behind it when penalised
   bool seg_attr_ens_half[2][5][2][2] = {};  // [NB - 2][order slot][forward, backward][penalised]: seg_attr for the ENS halves
   // The gate duration as a per-seed variable (qoc_set_time_scale): while ts_on, qoc_eval_dev runs the segmented
   // eval's TS instantiations (blkseg_eval_ts), which read τ_b from d_ts at launch and leave dJ_b/dτ_b behind it.  A
   // setting of the context: it survives qoc_set_generators, qoc_set_x0 and qoc_set_cost.  Allocated by the setter
-  // (counted in dev_bytes), freed when the scale is cleared and at qoc_destroy.
+  // (counted in info[3]), freed when the scale is cleared and at qoc_destroy.
   bool ts_on = false;
   bool ts_grad = false;              // d_ts + B holds an eval's dJ/dτ
-  double* d_ts = nullptr;            // 2 B: τ_b | dJ_b/dτ_b of the last eval under the scale
+  DevBuf<double> d_ts{mem, kCounted};            // 2 B: τ_b | dJ_b/dτ_b of the last eval under the scale
   bool seg_attr_ts[2][5][3][2] = {};  // seg_attr for the TS instantiations
-  int* h_flag = nullptr;             // host-mapped stale-u flag of the queued check (k_compare_u_flags)
+  DevBuf<int> h_flag{mem, kUncounted, hipHostMallocMapped | hipHostMallocCoherent};  // host-mapped stale-u flag of the queued check (k_compare_u_flags)
   int flag_turn = 0;                 // which of the two device flags d_flag[0 / 1] the next queued check writes
   hipEvent_t flag_ev = nullptr;      // recorded after that copy
-  double* d_J_scr = nullptr;         // B
-  cx<double>* d_coef_scr = nullptr;  // B x 2m
+  DevBuf<double> d_J_scr{mem, kCounted};         // B
+  DevBuf<cx<double>> d_coef_scr{mem, kCounted};  // B x 2m
   // every generator exactly skew-Hermitian (|A + A^H| <= 4 eps max|A|): the slice propagators are unitary, which the
   // segmented eval's backward relies on (λ_{k+1} = U_k λ_k)
   bool skew_exact = false;
-  cx<double>* d_coef_lam = nullptr;  // B x 2m: its λ_N coefficients
-  cx<double>* d_coef_mu = nullptr;  // B x 2m: the λ_N coefficients of the eval that left μ in d_L
+  DevBuf<cx<double>> d_coef_lam{mem, kCounted};  // B x 2m: its λ_N coefficients
+  DevBuf<cx<double>> d_coef_mu{mem, kCounted};  // B x 2m: the λ_N coefficients of the eval that left μ in d_L
   // generators with small invariant blocks (qoc_blk.hpp, detected at qoc_set_generators; QOC_BLOCKS=0 off): the
   // chains and the gradient run per block
   int blk_nb = 0;                // padded block size 2 / 3 / 4 (VALU lanes), 16 (MFMA block waves), 0: no block path
   int nblk = 0;                  // blocks
-  int* d_brow = nullptr;         // nblk x blk_nb rows of each block (-1 padding)
-  double2* d_gtab = nullptr;     // blocks of <= 3 rows: [nblk][3][blk_nb^2] shifted generator blocks (blk_detect)
+  DevBuf<int> d_brow{mem, kCounted};         // nblk x blk_nb rows of each block (-1 padding)
+  DevBuf<double2> d_gtab{mem, kCounted};     // blocks of <= 3 rows: [nblk][3][blk_nb^2] shifted generator blocks (blk_detect)
   int blk_jr = 0;                // chain kernels: 0 VALU lanes (k_blk_*), 1 / 4 MFMA block waves (k_blkrot_*<JR>)
   bool blk_real = false;         // MFMA block waves on the real embedding of blocks of <= 2 rows (k_blkrot_*<0>)
   int nwb = 0;                   // MFMA block waves per column pair
-  int* d_wrow = nullptr;         // nwb x 16 rows of each wave's state (-1 padding)
+  DevBuf<int> d_wrow{mem, kCounted};         // nwb x 16 rows of each wave's state (-1 padding)
   std::vector<int> h_wrow;       // host copy (blocks of 5..16 rows: one wave per block)
   // blocks of 5..16 rows with x_0 and X_target zero on their rows (blk_live): the waves of the others, the dead rows
   std::vector<int> h_wrow_live, h_dead_rows;
-  double* d_gc_part = nullptr;   // large-N gradient: per (slice, column block) partial traces (k_gen_contract2)
-  size_t gc_part_bytes = 0;
+  DevBuf<double> d_gc_part{mem, kCounted};   // large-N gradient: per (slice, column block) partial traces (k_gen_contract2)
   // the dead rows known to hold zeros (blk_zero_dead) and the state-shaped buffers, up to six, that hold them there:
   // a backward with an external λ_N or a co-state source (the only writers of nonzero values into rows whose x0 and
   // target are zero) sets dead_dirty, after which no buffer counts
   std::vector<int> h_dead_zeroed;
   const void* dead_bufs[6] = {};
   bool dead_dirty = true;
-  int* d_wrow_live = nullptr;
-  int* d_dead_rows = nullptr;
-  size_t blk_dev_bytes = 0;      // d_brow + d_wrow (counted in dev_bytes)
-  double* d_blkrec = nullptr;    // block propagators: B x Ntp x BLKU_REC step records (k_blku_rec, allocated on first use)
+  DevBuf<int> d_wrow_live{mem, kUncounted};
+  DevBuf<int> d_dead_rows{mem, kUncounted};
+  DevBuf<double> d_blkrec{mem, kCounted};    // block propagators: B x Ntp x BLKU_REC step records (k_blku_rec, allocated on first use)
   // multi-GPU epilogue (qoc_comm.hpp): RCCL communicator over the ranks' contexts
   ncclComm_t comm = nullptr;
   int world = 1, rank = 0;
   long long seed_offset = 0;   // global id of this context's seed 0
-  double* d_best = nullptr;    // [2 local | 2 x world gathered | 2 result]
-  unsigned int* d_done = nullptr;  // the segmented eval's workgroup counter (its last workgroup finds the best pair)
+  DevBuf<double> d_best{mem, kUncounted};    // [2 local | 2 x world gathered | 2 result]
+  DevBuf<unsigned int> d_done{mem, kUncounted};  // the segmented eval's workgroup counter (its last workgroup finds the best pair)
   double* best_out = nullptr;  // qoc_set_best_output's buffer
   // exact (Fréchet) gradient mode workspace, allocated on first use
-  void* d_fws = nullptr;
-  size_t fws_bytes = 0;
+  DevBuf<void> d_fws{mem, kUncounted};  // (grown when a call needs more)
   // the exact gradient as a series on dense generators (qoc_grad_rr.hpp k_grad_rr_x*, qoc_run_grad.hip grad_rr_exact);
   // its R(b) workspace is d_fws
   bool exact_series = true;             // QOC_GRAD_EXACT_SERIES=0 at qoc_create: the block exponential everywhere
-  unsigned long long* d_xn = nullptr;   // [0] max n_k, [1] Σ n_k of the last call, then B x Nt term counts (first use)
+  DevBuf<unsigned long long> d_xn{mem, kCounted};   // [0] max n_k, [1] Σ n_k of the last call, then B x Nt term counts (first use)
   size_t xws_budget = 0;                // workspace budget: min(2 GiB, free / 8) or QOC_GRAD_EXACT_WS_MB (first use)
   long long xs_stats[4] = {0, 0, 0, 0};  // qoc_exact_series_stats: units, Σ n_k, largest n_k, fallbacks over the cap
   // qoc_eval_envelope (qoc_ode_grad.hpp): the checkpoints (x_n, k1_n) every env C steps, scratch that no later call
-  // reads (grown on demand, not counted in dev_bytes: qoc_get_info reports what qoc_propagate_envelope would leave);
+  // reads (grown on demand, not counted in info[3]: qoc_get_info reports what qoc_propagate_envelope would leave);
   // the host form's parameters, gradient and caller's λ_N; QOC_ENV_CKPT at qoc_create forces the spacing (0: chosen per
   // call); the checkpoint budget min(1 GiB, free / 4) or QOC_ENV_WS_MB, read at first use
-  void* d_env_ws = nullptr;
-  size_t env_ws_bytes = 0;
-  double* d_env_p = nullptr;   // B x 64 parameters | B x 64 gradient
-  void* d_env_lam = nullptr;   // B x N x m
+  DevBuf<void> d_env_ws{mem, kUncounted};
+  DevBuf<double> d_env_p{mem, kUncounted};   // B x 64 parameters | B x 64 gradient
+  DevBuf<void> d_env_lam{mem, kUncounted};   // B x N x m
   int env_ckpt = 0;
   size_t env_budget = 0;
   // packed states (compress_states, src/utils.jl:96-109): two parity sectors share the kernels' columns, so the
@@ -366,7 +359,7 @@ struct qoc_ctx {
   std::vector<int> pk_cols[2];          // original columns of sector s: packed column i holds pk_cols[s][i]
   std::vector<int> pk_pos[2];           // m_user: packed column of original column c in sector s, or -1
   int zmap[4] = {0, 1, 2, 3};           // z-calibrated cost: original column c -> s m + i
-  unsigned char* d_rsec = nullptr;
+  DevBuf<unsigned char> d_rsec{mem, kCounted};
   bool grad_rr_any_m = false;           // the fused gradient fits apart from the column count
   // caller-layout copies, re-packed when the packing changes
   std::vector<double> h_gen, h_x0, h_Xt;

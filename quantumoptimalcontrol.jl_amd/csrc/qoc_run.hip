@@ -62,8 +62,8 @@ int run_forward(qoc_ctx* c) {
                                        (int)lds);
     if (r != hipSuccess) return r;
     hipLaunchKernelGGL((k_chain_fwd<T, S, JT, CB>), dim3(c->B), dim3(CHAIN_THREADS), lds, c->stream, c->N, c->m, c->Nt,
-                       (const cx<T>*)c->d_U, (const cx<T>*)c->d_x0, c->x0_per_seed, (cx<T>*)c->d_X,
-                       (const cx<T>*)c->d_Xt, c->cost_kind, c->cost_n, c->mu != 0.0 ? c->d_pmask : nullptr, c->mu,
+                       c->d_U.as<const cx<T>>(), c->d_x0.as<const cx<T>>(), c->x0_per_seed, c->d_X.as<cx<T>>(),
+                       c->d_Xt.as<const cx<T>>(), c->cost_kind, c->cost_n, c->mu != 0.0 ? c->d_pmask : nullptr, c->mu,
                        c->d_J, c->d_coef, sectors(c));
     return hipGetLastError();
   });
@@ -92,9 +92,9 @@ int run_backward(qoc_ctx* c, int order, double* d_dJdu) {
                                          hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
       if (r != hipSuccess) return r;
       hipLaunchKernelGGL((k_chain_bwd<T, S, JT, CB>), dim3(c->B), dim3(CHAIN_THREADS), lds, c->stream, c->N, c->m, c->Nt,
-                         (const cx<T>*)c->d_U, (const cx<T>*)c->d_X, (cx<T>*)c->d_L, (const cx<T>*)c->d_Xt,
+                         c->d_U.as<const cx<T>>(), c->d_X.as<const cx<T>>(), c->d_L.as<cx<T>>(), c->d_Xt.as<const cx<T>>(),
                          c->cost_kind, (const cx<double>*)c->d_coef, c->mu != 0.0 ? c->d_pmask : nullptr, c->mu,
-                         c->src_on ? (const cx<T>*)c->d_src : nullptr, sectors(c));
+                         c->src_on ? c->d_src.as<const cx<T>>() : nullptr, sectors(c));
       return hipGetLastError();
     });
     mark_end(c, mk);
@@ -132,7 +132,7 @@ int dense_gradient(qoc_ctx* c, int order, double* d_dJdu) {
   HIPCHK(c, hipFuncSetAttribute((const void*)k_grad<T>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   mk = mark_begin(c, 3);
   hipLaunchKernelGGL((k_grad<T>), dim3(c->B * c->Nt), dim3(GRAD_THREADS), lds, c->stream, c->N, c->m, c->nu, c->Nt,
-                     order, (const cx<T>*)c->d_A, c->d_u, (const cx<T>*)c->d_X, (const cx<T>*)c->d_L, d_dJdu);
+                     order, c->d_A.as<const cx<T>>(), c->d_u, c->d_X.as<const cx<T>>(), c->d_L.as<const cx<T>>(), d_dJdu);
   mark_end(c, mk);
   HIPCHK(c, hipGetLastError());
   return QOC_OK;

@@ -410,13 +410,13 @@ static int form_norm(qoc_ctx* c, long long u0, int cnt, cx<T>* out, unsigned lon
   const int N = c->N;
   const dim3 g2((unsigned)((N + 3) / 4), (unsigned)((cnt + FN2_SG - 1) / FN2_SG));
   if (c->nu <= 2 && N <= 256)
-    hipLaunchKernelGGL((k_form_norm2<T, 4>), g2, dim3(256), 0, c->stream, N, c->nu, u0, cnt, (const cx<T>*)c->d_A,
+    hipLaunchKernelGGL((k_form_norm2<T, 4>), g2, dim3(256), 0, c->stream, N, c->nu, u0, cnt, c->d_A.as<const cx<T>>(),
                        (const double*)c->d_u, out, nmax);
   else if (c->nu <= 2 && N <= 512)
-    hipLaunchKernelGGL((k_form_norm2<T, 8>), g2, dim3(256), 0, c->stream, N, c->nu, u0, cnt, (const cx<T>*)c->d_A,
+    hipLaunchKernelGGL((k_form_norm2<T, 8>), g2, dim3(256), 0, c->stream, N, c->nu, u0, cnt, c->d_A.as<const cx<T>>(),
                        (const double*)c->d_u, out, nmax);
   else
-    hipLaunchKernelGGL((k_form_norm<T>), dim3(cnt), dim3(256), 0, c->stream, N, c->nu, u0, (const cx<T>*)c->d_A,
+    hipLaunchKernelGGL((k_form_norm<T>), dim3(cnt), dim3(256), 0, c->stream, N, c->nu, u0, c->d_A.as<const cx<T>>(),
                        (const double*)c->d_u, out, nmax);
   HIPCHK(c, hipGetLastError());
   return QOC_OK;
@@ -430,30 +430,22 @@ static int gen_contract(qoc_ctx* c, long long u0, int cnt, const cx<T>* Mp, doub
   if (nu >= 1 && nu <= 2 && N <= 512) {
     const int ncb = (N + 3) / 4;
     const size_t need = (size_t)c->chunk * ncb * nu * sizeof(double);
-    if (need > c->gc_part_bytes) {
-      if (c->d_gc_part) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipFree(c->d_gc_part));
-        c->dev_bytes -= c->gc_part_bytes;
-      }
-      c->d_gc_part = nullptr;
-      c->gc_part_bytes = 0;
-      HIPCHK(c, hipMalloc((void**)&c->d_gc_part, need));
-      c->gc_part_bytes = need;
-      c->dev_bytes += need;
+    if (need > c->d_gc_part.bytes()) {
+      if (c->d_gc_part) HIPCHK(c, hipStreamSynchronize(c->stream));
+      HIPCHK(c, c->d_gc_part.grow(need));
     }
     const dim3 g2((unsigned)ncb, (unsigned)((cnt + GC2_SG - 1) / GC2_SG));
     if (N <= 256)
-      hipLaunchKernelGGL((k_gen_contract2<T, 4>), g2, dim3(256), 0, c->stream, N, nu, cnt, (const cx<T>*)c->d_A, Mp,
+      hipLaunchKernelGGL((k_gen_contract2<T, 4>), g2, dim3(256), 0, c->stream, N, nu, cnt, c->d_A.as<const cx<T>>(), Mp,
                          c->d_gc_part);
     else
-      hipLaunchKernelGGL((k_gen_contract2<T, 8>), g2, dim3(256), 0, c->stream, N, nu, cnt, (const cx<T>*)c->d_A, Mp,
+      hipLaunchKernelGGL((k_gen_contract2<T, 8>), g2, dim3(256), 0, c->stream, N, nu, cnt, c->d_A.as<const cx<T>>(), Mp,
                          c->d_gc_part);
     HIPCHK(c, hipGetLastError());
     const unsigned rb = (unsigned)std::min<long long>(((long long)cnt * nu + 255) / 256, 1024);
     hipLaunchKernelGGL(k_gen_reduce, dim3(rb), dim3(256), 0, c->stream, cnt, nu, ncb, u0, c->d_gc_part, d_dJdu);
   } else {
-    hipLaunchKernelGGL((k_gen_contract<T>), dim3(cnt), dim3(256), 0, c->stream, N, nu, u0, (const cx<T>*)c->d_A, Mp,
+    hipLaunchKernelGGL((k_gen_contract<T>), dim3(cnt), dim3(256), 0, c->stream, N, nu, u0, c->d_A.as<const cx<T>>(), Mp,
                        d_dJdu);
   }
   HIPCHK(c, hipGetLastError());
@@ -465,9 +457,9 @@ template <typename T>
 int big_expm_chunk(qoc_ctx* c, long long u0, int cnt) {
   const int N = c->N;
   const size_t NN = (size_t)N * N, esz = c->esz;
-  cx<T>* a0 = (cx<T>*)c->d_ws;
+  cx<T>* a0 = c->d_ws.as<cx<T>>();
   HIPCHK(c, hipMemsetAsync(c->d_red, 0, 2 * sizeof(double), c->stream));
-  if (int r = form_norm<T>(c, u0, cnt, a0, (unsigned long long*)c->d_red)) return r;
+  if (int r = form_norm<T>(c, u0, cnt, a0, c->d_red.as<unsigned long long>())) return r;
   if (c->big_rho_ok) {
     SpecBound sb{};
     for (int j = 0; j <= c->nu && j < 9; ++j) sb.rho[j] = c->big_rho[j];
@@ -515,13 +507,13 @@ int big_forward(qoc_ctx* c) {
   // costs
   const bool pen = c->mu != 0.0;
   if (pen) {
-    hipLaunchKernelGGL((k_penalty_sum<T>), dim3(B), dim3(256), 0, c->stream, N, m, Nt, (const cx<T>*)c->d_X,
+    hipLaunchKernelGGL((k_penalty_sum<T>), dim3(B), dim3(256), 0, c->stream, N, m, Nt, c->d_X.as<const cx<T>>(),
                        c->d_pmask, c->mu, c->d_J);
     HIPCHK(c, hipGetLastError());
   }
   if (c->cost_kind != QOC_COST_EXTERNAL) {
-    hipLaunchKernelGGL((k_terminal_cost<T>), dim3(B), dim3(256), 0, c->stream, N, m, Nt, (const cx<T>*)c->d_X,
-                       (const cx<T>*)c->d_Xt, c->cost_kind, c->cost_n, pen ? 1 : 0, c->d_J, c->d_coef, sectors(c));
+    hipLaunchKernelGGL((k_terminal_cost<T>), dim3(B), dim3(256), 0, c->stream, N, m, Nt, c->d_X.as<const cx<T>>(),
+                       c->d_Xt.as<const cx<T>>(), c->cost_kind, c->cost_n, pen ? 1 : 0, c->d_J, c->d_coef, sectors(c));
     HIPCHK(c, hipGetLastError());
   } else if (!pen) {
     HIPCHK(c, hipMemsetAsync(c->d_J, 0, (size_t)B * sizeof(double), c->stream));
@@ -539,18 +531,18 @@ int big_backward(qoc_ctx* c, int order, double* d_dJdu) {
   int r;
   int mk = mark_begin(c, 2);
   if (c->cost_kind != QOC_COST_EXTERNAL) {
-    hipLaunchKernelGGL((k_lambda_final<T>), dim3(eb), dim3(256), 0, c->stream, N, m, Nt, B, (const cx<T>*)c->d_Xt,
-                       (const cx<double>*)c->d_coef, (cx<T>*)c->d_L, sectors(c));
+    hipLaunchKernelGGL((k_lambda_final<T>), dim3(eb), dim3(256), 0, c->stream, N, m, Nt, B, c->d_Xt.as<const cx<T>>(),
+                       (const cx<double>*)c->d_coef, c->d_L.as<cx<T>>(), sectors(c));
     HIPCHK(c, hipGetLastError());
   }
   if (pen) {
     hipLaunchKernelGGL((k_penalty_grad<T>), dim3(eb), dim3(256), 0, c->stream, N, m, Nt, B, Nt,
-                       (const cx<T>*)c->d_X, c->d_pmask, 2.0 * c->mu, (cx<T>*)c->d_L);
+                       c->d_X.as<const cx<T>>(), c->d_pmask, 2.0 * c->mu, c->d_L.as<cx<T>>());
     HIPCHK(c, hipGetLastError());
   }
   if (c->src_on) {
-    hipLaunchKernelGGL((k_add_source<T>), dim3(eb), dim3(256), 0, c->stream, N, m, Nt, B, Nt, (const cx<T>*)c->d_src,
-                       (cx<T>*)c->d_L);
+    hipLaunchKernelGGL((k_add_source<T>), dim3(eb), dim3(256), 0, c->stream, N, m, Nt, B, Nt, c->d_src.as<const cx<T>>(),
+                       c->d_L.as<cx<T>>());
     HIPCHK(c, hipGetLastError());
   }
   // λ_k = U_k^H λ_{k+1} (+ dL/dx(x_k))
@@ -562,12 +554,12 @@ int big_backward(qoc_ctx* c, int order, double* d_dJdu) {
     if ((r = big_gemm<T>(c, 1, 0, g))) return r;
     if (pen) {
       hipLaunchKernelGGL((k_penalty_grad<T>), dim3(eb), dim3(256), 0, c->stream, N, m, Nt, B, k,
-                         (const cx<T>*)c->d_X, c->d_pmask, 2.0 * c->mu, (cx<T>*)c->d_L);
+                         c->d_X.as<const cx<T>>(), c->d_pmask, 2.0 * c->mu, c->d_L.as<cx<T>>());
       HIPCHK(c, hipGetLastError());
     }
     if (c->src_on) {
-      hipLaunchKernelGGL((k_add_source<T>), dim3(eb), dim3(256), 0, c->stream, N, m, Nt, B, k, (const cx<T>*)c->d_src,
-                         (cx<T>*)c->d_L);
+      hipLaunchKernelGGL((k_add_source<T>), dim3(eb), dim3(256), 0, c->stream, N, m, Nt, B, k, c->d_src.as<const cx<T>>(),
+                         c->d_L.as<cx<T>>());
       HIPCHK(c, hipGetLastError());
     }
   }
@@ -593,7 +585,7 @@ int big_backward(qoc_ctx* c, int order, double* d_dJdu) {
   if (env_set("QOC_GRAD_SANDWICH")) sandwich = o == 3 && env_int("QOC_GRAD_SANDWICH", 0) != 0;
   for (long long u0 = 0; u0 < units; u0 += c->chunk) {
     const int cnt = (int)std::min<long long>(c->chunk, units - u0);
-    if (int r = form_norm<T>(c, u0, cnt, (cx<T>*)((char*)c->d_ws + offX * esz), nullptr)) return r;
+    if (int r = form_norm<T>(c, u0, cnt, (cx<T>*)(c->d_ws.as<char>() + offX * esz), nullptr)) return r;
     const Opd Xk = mk_opd(c->d_ws, offX, esz, (long long)NN);
     if (sandwich) {  // workspace: X, then three N x N blocks per item (G / R, T1 / M', S) — 4 NN of the 8 NN
       const size_t offG = C * NN, offT = 2 * C * NN, offS = 3 * C * NN;
@@ -617,7 +609,7 @@ int big_backward(qoc_ctx* c, int order, double* d_dJdu) {
       g = gemm_args(N, N, N, cnt);  // M' = X^H S / 6 + R   (over T1)
       g.A = Xk; g.B = Sk; g.C1 = Tk; g.alpha1 = 1.0 / 6; g.nY = 1; g.Y[0] = Gk; g.w1[0] = 1.0;
       if ((r = big_gemm<T>(c, 1, 0, g))) return r;
-      if ((r = gen_contract<T>(c, u0, cnt, (const cx<T>*)((char*)c->d_ws + offT * esz), d_dJdu))) return r;
+      if ((r = gen_contract<T>(c, u0, cnt, (const cx<T>*)(c->d_ws.as<char>() + offT * esz), d_dJdu))) return r;
       continue;
     }
     auto Pa = [&](int a) { return mk_opd(c->d_ws, offP + a * Nm, esz, (long long)(o * Nm)); };
@@ -678,7 +670,7 @@ int big_backward(qoc_ctx* c, int order, double* d_dJdu) {
     g.B = mk_opd(c->d_ws, offP, esz, (long long)(o * Nm));
     g.C1 = mk_opd(c->d_ws, offM, esz, (long long)NN);
     if ((r = big_gemm<T>(c, 0, 1, g))) return r;  // M' = W P^H
-    if ((r = gen_contract<T>(c, u0, cnt, (const cx<T>*)((char*)c->d_ws + offM * esz), d_dJdu))) return r;
+    if ((r = gen_contract<T>(c, u0, cnt, (const cx<T>*)(c->d_ws.as<char>() + offM * esz), d_dJdu))) return r;
   }
   mark_end(c, mk);
   return QOC_OK;
@@ -762,14 +754,8 @@ int frechet_grad(qoc_ctx* c, double* d_dJdu) {
   const size_t budget = std::min<size_t>(4ull << 30, std::max<size_t>(freeb / 8, per_item));
   const int fch = (int)std::max<long long>(1, std::min<long long>({(long long)(budget / per_item), units, 16384LL}));
   const size_t need = (size_t)fch * per_item + nu * NN * esz + 64 * sizeof(double);
-  if (c->fws_bytes < need) {
-    if (c->d_fws) HIPCHK(c, hipFree(c->d_fws));
-    c->d_fws = nullptr;
-    c->fws_bytes = 0;
-    HIPCHK(c, hipMalloc(&c->d_fws, need));
-    c->fws_bytes = need;
-  }
-  char* p = (char*)c->d_fws;
+  HIPCHK(c, c->d_fws.grow(need));
+  char* p = c->d_fws.as<char>();
   cx<T>* blocks = (cx<T>*)p;
   p += (size_t)fch * BB * esz;
   cx<T>* E = (cx<T>*)p;
@@ -784,13 +770,13 @@ int frechet_grad(qoc_ctx* c, double* d_dJdu) {
   double* alpha = (double*)p;
   p += (size_t)fch * sizeof(double);
   double* red = (double*)p;  // fch + 8 doubles
-  hipLaunchKernelGGL((k_transpose_gens<T>), dim3(256), dim3(256), 0, c->stream, N, nu, (const cx<T>*)c->d_A, At);
+  hipLaunchKernelGGL((k_transpose_gens<T>), dim3(256), dim3(256), 0, c->stream, N, nu, c->d_A.as<const cx<T>>(), At);
   HIPCHK(c, hipGetLastError());
   int r;
   for (long long u0 = 0; u0 < units; u0 += fch) {
     const int cnt = (int)std::min<long long>(fch, units - u0);
     hipLaunchKernelGGL((k_frechet_build<T>), dim3(cnt), dim3(256), 0, c->stream, N, c->m, nu, c->Nt, u0,
-                       (const cx<T>*)c->d_A, (const double*)c->d_u, (const cx<T>*)c->d_X, (const cx<T>*)c->d_L,
+                       c->d_A.as<const cx<T>>(), (const double*)c->d_u, c->d_X.as<const cx<T>>(), c->d_L.as<const cx<T>>(),
                        blocks, alpha);
     HIPCHK(c, hipGetLastError());
     if (small) {
@@ -902,10 +888,10 @@ hipError_t launch_gen_aux(qoc_ctx* c) {
   const unsigned blocks = (unsigned)std::min<size_t>(((c->nu + 1) * NN + 255) / 256, 2048);
   if (c->prec == QOC_FP64)
     hipLaunchKernelGGL((k_gen_aux<double>), dim3(blocks), dim3(256), 0, c->stream, c->N, c->nu,
-                       (const cx<double>*)c->d_A, (cx<double>*)c->d_AH, (cx<double>*)c->d_Cst);
+                       c->d_A.as<const cx<double>>(), c->d_AH.as<cx<double>>(), c->d_Cst.as<cx<double>>());
   else
     hipLaunchKernelGGL((k_gen_aux<float>), dim3(blocks), dim3(256), 0, c->stream, c->N, c->nu,
-                       (const cx<float>*)c->d_A, (cx<float>*)c->d_AH, (cx<float>*)c->d_Cst);
+                       c->d_A.as<const cx<float>>(), c->d_AH.as<cx<float>>(), c->d_Cst.as<cx<float>>());
   return hipGetLastError();
 }
 

@@ -110,36 +110,25 @@ int blk_detect(qoc_ctx* c) {
   c->h_wrow_live.clear();
   c->h_dead_rows.clear();
   c->dead_dirty = true;
-  for (int** p : {&c->d_brow, &c->d_wrow, &c->d_wrow_live, &c->d_dead_rows})
-    if (*p) {
-      HIPCHK(c, hipFree(*p));
-      *p = nullptr;
-    }
-  c->dev_bytes -= c->blk_dev_bytes;  // the row lists of a previous qoc_set_generators
-  c->blk_dev_bytes = 0;
-  HIPCHK(c, hipMalloc((void**)&c->d_brow, brow.size() * sizeof(int)));
+  // the row lists and the table of a previous qoc_set_generators go first
+  for (DevBufBase* b : {(DevBufBase*)&c->d_brow, (DevBufBase*)&c->d_wrow, (DevBufBase*)&c->d_wrow_live,
+                        (DevBufBase*)&c->d_dead_rows, (DevBufBase*)&c->d_gtab})
+    b->release();
+  HIPCHK(c, c->d_brow.alloc(brow.size() * sizeof(int)));
   HIPCHK(c, hipMemcpy(c->d_brow, brow.data(), brow.size() * sizeof(int), hipMemcpyHostToDevice));
-  c->blk_dev_bytes += brow.size() * sizeof(int);
-  if (c->d_gtab) {
-    HIPCHK(c, hipFree(c->d_gtab));
-    c->d_gtab = nullptr;
-  }
   if (NB <= 3) {
     // the segmented eval's generator blocks, block-major [nblk][3][NB^2]: the entries of the shifted generators
     // Ã_j = A_j - μ_j I (the values qoc_set_generators uploads to d_At: the same subtraction) on each block's rows,
     // zero for j > nu and for a padded row; its prologue copies the table instead of gathering through d_brow
     std::vector<double> tab((size_t)nblk * 3 * NB * NB * 2, 0.0);
     blk_gen_table(c, brow, NB, nblk, c->h_gen.data(), c->tprm.mur, c->tprm.mui, tab.data());
-    HIPCHK(c, hipMalloc((void**)&c->d_gtab, tab.size() * sizeof(double)));
+    HIPCHK(c, c->d_gtab.alloc(tab.size() * sizeof(double)));
     HIPCHK(c, hipMemcpy(c->d_gtab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
-    c->blk_dev_bytes += tab.size() * sizeof(double);
   }
   if (jr || real) {
-    HIPCHK(c, hipMalloc((void**)&c->d_wrow, wrow.size() * sizeof(int)));
+    HIPCHK(c, c->d_wrow.alloc(wrow.size() * sizeof(int)));
     HIPCHK(c, hipMemcpy(c->d_wrow, wrow.data(), wrow.size() * sizeof(int), hipMemcpyHostToDevice));
-    c->blk_dev_bytes += wrow.size() * sizeof(int);
   }
-  c->dev_bytes += c->blk_dev_bytes;
   c->blk_nb = NB;
   c->nblk = nblk;
   c->blk_jr = jr;
@@ -253,14 +242,10 @@ int blk_live(qoc_ctx* c, BlkArgs& bk, bool all) {
   if (all || !blk_live_rows(c, wl, dead)) return QOC_OK;
   if (wl != c->h_wrow_live || dead != c->h_dead_rows) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    for (int** p : {&c->d_wrow_live, &c->d_dead_rows})
-      if (*p) {
-        HIPCHK(c, hipFree(*p));
-        *p = nullptr;
-      }
-    HIPCHK(c, hipMalloc((void**)&c->d_wrow_live, wl.size() * sizeof(int)));
+    c->d_dead_rows.release();
+    HIPCHK(c, c->d_wrow_live.alloc(wl.size() * sizeof(int)));
     HIPCHK(c, hipMemcpy(c->d_wrow_live, wl.data(), wl.size() * sizeof(int), hipMemcpyHostToDevice));
-    HIPCHK(c, hipMalloc((void**)&c->d_dead_rows, dead.size() * sizeof(int)));
+    HIPCHK(c, c->d_dead_rows.alloc(dead.size() * sizeof(int)));
     HIPCHK(c, hipMemcpy(c->d_dead_rows, dead.data(), dead.size() * sizeof(int), hipMemcpyHostToDevice));
     c->h_wrow_live = wl;
     c->h_dead_rows = dead;
@@ -428,9 +413,9 @@ int blk_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu) {
   if (blk_big(c)) {  // the first two products of every slice for k_grad_rr_c (forward -> d_pws, μ -> d_gws)
     const size_t bufN = (size_t)c->N * ((size_t)c->B * (c->Nt + 1) * c->m);
     gf.cap1 = c->d_pws;
-    gf.cap2 = (cx<double>*)c->d_pws + bufN;
+    gf.cap2 = c->d_pws.as<cx<double>>() + bufN;
     gb.cap1 = c->d_gws;
-    gb.cap2 = (cx<double>*)c->d_gws + bufN;
+    gb.cap2 = c->d_gws.as<cx<double>>() + bufN;
   }
   BlkArgs bk = blk_args(c);
   if ((r = blk_live(c, bk))) return r;

@@ -59,24 +59,16 @@ static void blkp_forward_done(qoc_ctx* c, int ichain) {
 // the propagator store d_blkU of at least `bytes` (reallocated when a larger batch part or block layout needs more);
 // soft: a failed allocation is no error (returns 1: the caller takes the Chebyshev block chains instead)
 static int blkp_ensure_store(qoc_ctx* c, size_t bytes, bool soft) {
-  if (c->blkU_bytes >= bytes) return QOC_OK;
+  if (c->d_blkU.bytes() >= bytes) return QOC_OK;
   if (c->d_blkU) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
     if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
-    HIPCHK(c, hipFree(c->d_blkU));
-    c->d_blkU = nullptr;
-    c->dev_bytes -= c->blkU_bytes;
-    c->blkU_bytes = 0;
   }
-  const hipError_t e = hipMalloc((void**)&c->d_blkU, bytes);
+  const hipError_t e = c->d_blkU.grow(bytes);
   if (e != hipSuccess) {
-    c->d_blkU = nullptr;
-    (void)hipGetLastError();  // clear the sticky error of the failed allocation
     if (soft) return 1;
     return fail(c, QOC_ERR_HIP, "stored block propagators (%zu bytes): %s", bytes, hipGetErrorString(e));
   }
-  c->blkU_bytes = bytes;
-  c->dev_bytes += bytes;
   return QOC_OK;
 }
 
@@ -170,12 +162,8 @@ static int blkp_cheb_table(qoc_ctx* c, int cm, double crmax) {
         row[4 + qq * cm + jj] = (double)br;
       }
   }
-  if (c->d_blkp_ctab) {
-    HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipFree(c->d_blkp_ctab));
-    c->d_blkp_ctab = nullptr;
-  }
-  HIPCHK(c, hipMalloc((void**)&c->d_blkp_ctab, tab.size() * sizeof(double)));
+  if (c->d_blkp_ctab) HIPCHK(c, hipStreamSynchronize(c->stream));
+  HIPCHK(c, c->d_blkp_ctab.alloc(tab.size() * sizeof(double)));
   HIPCHK(c, hipMemcpy(c->d_blkp_ctab, tab.data(), tab.size() * sizeof(double), hipMemcpyHostToDevice));
   c->ctab_cm = cm;
   c->ctab_rmax = crmax;
@@ -240,8 +228,8 @@ static int blkp_urange(qoc_ctx* c, double& lo, double& hi) {
   const long long n = (long long)c->B * c->Nt * c->nu;
   const int grid = (int)std::max<long long>(1, std::min<long long>(256, (n + 255) / 256));
   if (!c->d_minmax) {
-    HIPCHK(c, hipMalloc((void**)&c->d_minmax, 512 * sizeof(double)));
-    HIPCHK(c, hipHostMalloc((void**)&c->h_minmax, 512 * sizeof(double), hipHostMallocDefault));
+    HIPCHK(c, c->h_minmax.alloc(512 * sizeof(double)));
+    HIPCHK(c, c->d_minmax.alloc(512 * sizeof(double)));
   }
   hipLaunchKernelGGL(k_minmax, dim3(grid), dim3(256), 0, c->stream, (const double*)c->d_u, n, c->d_minmax);
   HIPCHK(c, hipGetLastError());
@@ -425,15 +413,12 @@ static int blkp_interp_coeffs(qoc_ctx* c, const std::vector<int>& wrow, double l
           h[nsoff + (size_t)i * 128 + blkp_sym_slot(a, b2, nl)] =
               make_double2((double)Gr[i][a * 16 + b2], (double)Gi[i][a * 16 + b2]);
   const size_t bytes = h.size() * sizeof(double2);
-  if (c->blkp_M_bytes < bytes) {
+  if (c->d_blkp_M.bytes() < bytes) {
     if (c->d_blkp_M) {
       HIPCHK(c, hipStreamSynchronize(c->stream));
       if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
-      HIPCHK(c, hipFree(c->d_blkp_M));
-      c->d_blkp_M = nullptr;
     }
-    HIPCHK(c, hipMalloc((void**)&c->d_blkp_M, bytes));
-    c->blkp_M_bytes = bytes;
+    HIPCHK(c, c->d_blkp_M.grow(bytes));
   }
   HIPCHK(c, hipMemcpy(c->d_blkp_M, h.data(), bytes, hipMemcpyHostToDevice));
   c->int_D = D;
@@ -535,7 +520,7 @@ static int blkp_plan(qoc_ctx* c, const BlkArgs& bk, int parts, BlkpPlan& pl, boo
   a.tail = std::max(0, env_int("QOC_BLKP_TAIL", a.rcap > 0.0 ? 3 : 0));
   if (a.tail > 0) blkp_theta_table(a.tail, a.theta);
   a.wrow = bk.wrow;
-  a.At = (const cx<double>*)c->d_At;
+  a.At = c->d_At.as<const cx<double>>();
   a.u = c->d_u;
   for (int j = 0; j < 3; ++j) {
     a.mur[j] = j <= c->nu ? c->tprm.mur[j] : 0.0;
@@ -648,10 +633,10 @@ static int blkp_launch_grad(qoc_ctx* c, const BlkArgs& bk, double* d_dJdu, const
   ga.Nt = c->Nt;
   ga.nwb = bk.nwb;
   ga.wrow = bk.wrow;
-  ga.A = (const cx<double>*)c->d_A;
+  ga.A = c->d_A.as<const cx<double>>();
   ga.u = c->d_u;
-  ga.X = (const cx<double>*)c->d_X;
-  ga.L = (const cx<double>*)c->d_L;
+  ga.X = c->d_X.as<const cx<double>>();
+  ga.L = c->d_L.as<const cx<double>>();
   ga.coef = c->d_coef;
   ga.dJdu = d_dJdu;
   ga.tiles = (long long)c->B * ((c->Nt + 15) / 16);
@@ -721,8 +706,8 @@ static int blkp_launch_grad_exact(qoc_ctx* c, const BlkArgs& bk, double* d_dJdu,
   const bool sym = c->int_sym && bk.nwb == 1 && env_int("QOC_BLKP_ISYM", 1) != 0;
   ga.Nc = c->d_blkp_M + (sym ? c->int_nsoff : c->int_noff);
   ga.nl = sym ? c->int_nl : 0;
-  ga.X = (const cx<double>*)c->d_X;
-  ga.L = (const cx<double>*)c->d_L;
+  ga.X = c->d_X.as<const cx<double>>();
+  ga.L = c->d_L.as<const cx<double>>();
   ga.coef = c->d_coef;
   ga.dJdu = d_dJdu;
   ga.stale = stale;
@@ -774,14 +759,9 @@ static int blkp_launch_ichain(qoc_ctx* c, const TChainArgs& gf, const TChainArgs
                               const BlkpIntArgs& ia0, bool dual, int dir, const int* stale, const BlkpPen* pp = nullptr) {
   // the slices' e^{μ(u_k)} first (one sincos per (seed, slice) instead of one per chain wave)
   const size_t nph = (size_t)c->B * c->Nt;
-  if (c->blkp_ph_n < nph) {
-    if (c->d_blkp_ph) {
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      HIPCHK(c, hipFree(c->d_blkp_ph));
-      c->d_blkp_ph = nullptr;
-    }
-    HIPCHK(c, hipMalloc((void**)&c->d_blkp_ph, nph * sizeof(double2)));
-    c->blkp_ph_n = nph;
+  if (c->d_blkp_ph.bytes() < nph * sizeof(double2)) {
+    if (c->d_blkp_ph) HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->d_blkp_ph.grow(nph * sizeof(double2)));
   }
   BlkpIntArgs ia = ia0;
   ia.ph = c->d_blkp_ph;
@@ -872,7 +852,7 @@ int blkp_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu, const BlkArgs& b
   for (int p = 0; p < parts; ++p) {
     const int s0 = (int)((long long)c->B * p / parts), s1 = (int)((long long)c->B * (p + 1) / parts);
     if (s1 <= s0) continue;
-    double2* const U = (double2*)c->d_blkU + (size_t)(p % nslab) * slab;
+    double2* const U = c->d_blkU.as<double2>() + (size_t)(p % nslab) * slab;
     if (p >= 2) HIPCHK(c, hipStreamWaitEvent(c->stream, c->sync_ev[parts + p - 2], 0));  // slab p % 2 read out
     if ((r = blkp_launch_exp(c, pl, (long long)s0 * per_seed, (long long)s1 * per_seed, U, (long long)s0 * per_seed)))
       return r;
@@ -954,7 +934,7 @@ int blkp_forward(qoc_ctx* c) {
     HIPCHK(c, hipStreamWaitEvent(c->stream2, c->sync_ev[parts], 0));
   }
   hipStream_t cs = parts > 1 ? c->stream2 : c->stream;
-  double2* const U = (double2*)c->d_blkU;
+  double2* const U = c->d_blkU.as<double2>();
   for (int p = 0; p < parts; ++p) {
     const int s0 = (int)((long long)c->B * p / parts), s1 = (int)((long long)c->B * (p + 1) / parts);
     if (s1 <= s0) continue;
@@ -1008,7 +988,7 @@ int blkp_backward(qoc_ctx* c, int order, double* d_dJdu, const int* stale) {
     if (exact && !pl.interp) return 1;            // this layout's series did not converge: nothing launched
     const long long units = (long long)c->B * c->Nt * bk.nwb;
     if ((r = blkp_ensure_store(c, (size_t)units * 256 * sizeof(double2), false))) return r;
-    if ((r = blkp_launch_exp(c, pl, 0, units, (double2*)c->d_blkU, 0))) return r;
+    if ((r = blkp_launch_exp(c, pl, 0, units, c->d_blkU.as<double2>(), 0))) return r;
     c->fwd.ichain = false;  // the forward's leftovers are now the stored propagators of this layout
     c->fwd.formed_ichain = 0;
     c->fwd.nwb = bk.nwb;
@@ -1026,7 +1006,7 @@ int blkp_backward(qoc_ctx* c, int order, double* d_dJdu, const int* stale) {
   } else {
     BlkpPlan pl;
     if ((r = blkp_plan(c, bk, 1, pl, false))) return r;
-    if ((r = blkp_launch_chain<false>(c, pl, gb, bk, (const double2*)c->d_blkU, 0, c->B, 0, c->stream, stale, pen)))
+    if ((r = blkp_launch_chain<false>(c, pl, gb, bk, c->d_blkU.as<const double2>(), 0, c->B, 0, c->stream, stale, pen)))
       return r;
   }
   if ((r = exact ? blkp_launch_grad_exact(c, bk, d_dJdu, stale, lam ? nullptr : c->d_coef_mu, lam)

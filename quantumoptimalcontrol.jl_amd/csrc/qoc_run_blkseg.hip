@@ -89,9 +89,8 @@ bool blkseg_ok(const qoc_ctx* c, int order) {
 static int ensure_lazy_bufs(qoc_ctx* c) {
   const size_t nu_t = (size_t)c->B * c->nu * c->Nt, ncf = (size_t)c->B * 2 * c->m_user;
   if (!c->d_u_lam) {
-    HIPCHK(c, hipMalloc((void**)&c->d_u_lam, nu_t * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->d_coef_lam, ncf * sizeof(cx<double>)));
-    c->dev_bytes += nu_t * sizeof(double) + ncf * sizeof(cx<double>);
+    HIPCHK(c, c->d_coef_lam.alloc(ncf * sizeof(cx<double>)));
+    HIPCHK(c, c->d_u_lam.alloc(nu_t * sizeof(double)));
   }
   return QOC_OK;
 }
@@ -119,12 +118,12 @@ static int blkseg_params(qoc_ctx* c, const BlksegShape& s, BlksegParams& sp) {
   }
   // the best (J, seed) for qoc_allgather_best_dev, found by the launch's last workgroup
   if (!c->d_best) {  // no communicator yet: this context alone (the epilogue's own layout)
-    HIPCHK(c, hipMalloc((void**)&c->d_best, 6 * sizeof(double)));
+    HIPCHK(c, c->d_best.alloc(6 * sizeof(double)));
     c->world = 1;
     c->rank = 0;
   }
   if (!c->d_done) {
-    HIPCHK(c, hipMalloc((void**)&c->d_done, sizeof(unsigned int)));
+    HIPCHK(c, c->d_done.alloc(sizeof(unsigned int)));
     HIPCHK(c, hipMemsetAsync(c->d_done, 0, sizeof(unsigned int), c->stream));
   }
   sp.done = c->d_done;
@@ -328,17 +327,11 @@ int blkseg_eval_ens(qoc_ctx* c, int order, const double* d_u, double* d_J, doubl
   if (route == 2) {
     // (the setters sized G for the shape and the penalty of their time; a penalty set since may need D behind it)
     const size_t gbytes = (blkseg_pen(c) ? 2 : 1) * gcount * sizeof(double2);
-    if (c->ens_gseg_bytes < gbytes) {
-      double2* q = nullptr;
-      HIPCHK(c, hipMalloc((void**)&q, gbytes));
-      if (c->d_ens_gseg) {
-        HIPCHK(c, hipStreamSynchronize(c->stream));
-        HIPCHK(c, hipFree(c->d_ens_gseg));
-      }
-      c->dev_bytes += gbytes - c->ens_gseg_bytes;
-      c->ens_risk_bytes += gbytes - c->ens_gseg_bytes;
-      c->d_ens_gseg = q;
-      c->ens_gseg_bytes = gbytes;
+    if (c->d_ens_gseg.bytes() < gbytes) {  // (the new one first: a failure leaves the old one in place)
+      DevBuf<double2> q;
+      HIPCHK(c, q.alloc(gbytes));
+      if (c->d_ens_gseg) HIPCHK(c, hipStreamSynchronize(c->stream));
+      c->d_ens_gseg.adopt(std::move(q));
     }
   }
   sp.u = d_u;
@@ -396,17 +389,9 @@ bool blkseg_ts_ok(const qoc_ctx* c, int order) { return c->ts_on && c->ens_E == 
 static int blkseg_gseg_buf(qoc_ctx* c, const BlksegShape& s, size_t& gcount) {
   gcount = (size_t)c->B * s.S * c->nblk * c->blk_nb * c->blk_nb;
   const size_t gbytes = (blkseg_pen(c) ? 2 : 1) * gcount * sizeof(double2);
-  if (c->gseg_bytes < gbytes) {  // a new block layout (qoc_set_generators) or a penalty may need more
-    if (c->d_gseg) {
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      HIPCHK(c, hipFree(c->d_gseg));
-      c->d_gseg = nullptr;
-      c->dev_bytes -= c->gseg_bytes;
-      c->gseg_bytes = 0;
-    }
-    HIPCHK(c, hipMalloc((void**)&c->d_gseg, gbytes));
-    c->gseg_bytes = gbytes;
-    c->dev_bytes += gbytes;
+  if (c->d_gseg.bytes() < gbytes) {  // a new block layout (qoc_set_generators) or a penalty may need more
+    if (c->d_gseg) HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->d_gseg.grow(gbytes));
   }
   return QOC_OK;
 }

@@ -101,11 +101,7 @@ static BlkuParams blku_params(const qoc_ctx* c, const BlkuShape& s, double* d_dJ
 // the step records of every (seed, slice) of the current u (k_blku_rec); count: add Σ P 2^J to the terms counter
 static int blku_records(qoc_ctx* c, BlkuParams& bp, bool count, const double* d_u = nullptr) {
   const long long total = (long long)c->B * blku_ntp(c);
-  if (!c->d_blkrec) {
-    const size_t bytes = (size_t)total * BLKU_REC * sizeof(double);
-    HIPCHK(c, hipMalloc((void**)&c->d_blkrec, bytes));
-    c->dev_bytes += bytes;
-  }
+  if (!c->d_blkrec) HIPCHK(c, c->d_blkrec.alloc((size_t)total * BLKU_REC * sizeof(double)));
   bp.rec = c->d_blkrec;
   BlkuParams rp = bp;
   rp.terms = count ? c->d_terms : nullptr;
@@ -251,9 +247,8 @@ static int blku_bwdg(qoc_ctx* c, int order, double* d_dJdu, const double2* Uin =
   // what qoc_get_costates needs to rebuild λ: this u and the λ_N coefficients (external λ_N stays in d_L)
   const size_t nu_t = (size_t)c->B * c->nu * c->Nt, ncf = (size_t)c->B * 2 * c->m;
   if (!c->d_u_lam) {
-    HIPCHK(c, hipMalloc((void**)&c->d_u_lam, nu_t * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->d_coef_lam, ncf * sizeof(cx<double>)));
-    c->dev_bytes += nu_t * sizeof(double) + ncf * sizeof(cx<double>);
+    HIPCHK(c, c->d_coef_lam.alloc(ncf * sizeof(cx<double>)));
+    HIPCHK(c, c->d_u_lam.alloc(nu_t * sizeof(double)));
   }
   HIPCHK(c, hipMemcpyAsync(c->d_u_lam, c->d_u, nu_t * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(c->d_coef_lam, c->d_coef, ncf * sizeof(cx<double>), hipMemcpyDeviceToDevice, c->stream));
@@ -265,9 +260,8 @@ static int blku_bwdg(qoc_ctx* c, int order, double* d_dJdu, const double2* Uin =
 // the block forward chain on d_u into d_X, J and the coefficients into scratch
 static int blku_states_of(qoc_ctx* c, const double* d_u) {
   if (!c->d_J_scr) {
-    HIPCHK(c, hipMalloc((void**)&c->d_J_scr, (size_t)c->B * sizeof(double)));
-    HIPCHK(c, hipMalloc((void**)&c->d_coef_scr, (size_t)c->B * 2 * c->m_user * sizeof(cx<double>)));
-    c->dev_bytes += (size_t)c->B * (sizeof(double) + 2 * c->m_user * sizeof(cx<double>));
+    HIPCHK(c, c->d_coef_scr.alloc((size_t)c->B * 2 * c->m_user * sizeof(cx<double>)));
+    HIPCHK(c, c->d_J_scr.alloc((size_t)c->B * sizeof(double)));
   }
   TChainArgs g = tchain_args(c);
   g.J = c->d_J_scr;
@@ -351,26 +345,18 @@ int blku_eval_concurrent(qoc_ctx* c, int order, double* d_dJdu) {
   const bool fused = blku_fused_ok(c, order);
   const bool storeu = fused && blku_shape(c, true, true).S == 1 && !env_is("QOC_BLKU_STOREU", "0");
   const size_t ubytes = (size_t)c->B * c->Nt * c->blk_nb * c->blk_nb * c->nblk * sizeof(double2);
-  if (storeu && c->blkU_bytes < ubytes) {  // a new block layout (qoc_set_generators) may need more
-    if (c->d_blkU) {
-      HIPCHK(c, hipStreamSynchronize(c->stream));
-      HIPCHK(c, hipFree(c->d_blkU));
-      c->d_blkU = nullptr;
-      c->dev_bytes -= c->blkU_bytes;
-      c->blkU_bytes = 0;
-    }
-    HIPCHK(c, hipMalloc((void**)&c->d_blkU, ubytes));
-    c->blkU_bytes = ubytes;
-    c->dev_bytes += ubytes;
+  if (storeu && c->d_blkU.bytes() < ubytes) {  // a new block layout (qoc_set_generators) may need more
+    if (c->d_blkU) HIPCHK(c, hipStreamSynchronize(c->stream));
+    HIPCHK(c, c->d_blkU.grow(ubytes));
   }
-  bp.Uout = storeu ? (double2*)c->d_blkU : nullptr;
+  bp.Uout = storeu ? c->d_blkU.as<double2>() : nullptr;
   const int mk = mark_begin(c, 1);
   const hipError_t e = blku_launch_fwd(c, s, bp);
   mark_end(c, mk);
   if (e != hipSuccess) return fail(c, QOC_ERR_HIP, "k_blku_fwd launch: %s", hipGetErrorString(e));
   c->props_since_reset++;
   if (fused) {
-    r = blku_bwdg(c, order, d_dJdu, storeu ? (const double2*)c->d_blkU : nullptr);
+    r = blku_bwdg(c, order, d_dJdu, storeu ? c->d_blkU.as<const double2>() : nullptr);
   } else {
     const int mb = mark_begin(c, 2);
     const hipError_t eb = blku_launch_bwd(c, tchain_args(c), s, bp, false);

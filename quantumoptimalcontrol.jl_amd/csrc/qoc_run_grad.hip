@@ -16,31 +16,31 @@ int grad_rr_launch(qoc_ctx* c, double* d_dJdu, hipStream_t st, int k0, int nk, i
   const int per_cu = lds <= 80 * 1024 ? 2 : 1;
   const int grid = (int)std::max<long long>(1, std::min<long long>((ntiles + 3) / 4, (long long)c->ncu * per_cu));
   const size_t bufN = (size_t)N * ((size_t)B * (Nt + 1) * m);
-  cx<T>* W0 = (cx<T>*)c->d_gws;
+  cx<T>* W0 = c->d_gws.as<cx<T>>();
   cx<T>* W1 = W0 + bufN;
   // mode 0: q + p;  1: state side only (k_grad_rr_s -> P1, P2 in d_pws);  2: q + p reading P1, P2
-  cx<T>* P1 = (cx<T>*)c->d_pws;
+  cx<T>* P1 = c->d_pws.as<cx<T>>();
   cx<T>* P2 = P1 ? P1 + bufN : nullptr;
   if (mode == 1) {
     HIPCHK(c, hipFuncSetAttribute((const void*)k_grad_rr_s<T, NT, KS, NU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((k_grad_rr_s<T, NT, KS, NU>), dim3(grid), dim3(256), lds, st, N, m, Nt, B, k0, nk,
-                       (const cx<T>*)c->d_A, c->d_u, (const cx<T>*)c->d_X, P1, P2);
+                       c->d_A.as<const cx<T>>(), c->d_u, c->d_X.as<const cx<T>>(), P1, P2);
     HIPCHK(c, hipGetLastError());
     return QOC_OK;
   }
   HIPCHK(c, hipFuncSetAttribute((const void*)k_grad_rr_q<T, NT, KS, NU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   hipLaunchKernelGGL((k_grad_rr_q<T, NT, KS, NU>), dim3(grid), dim3(256), lds, st, N, m, Nt, B, k0, nk,
-                     (const cx<T>*)c->d_A, c->d_u, (const cx<T>*)c->d_L, W0, W1);
+                     c->d_A.as<const cx<T>>(), c->d_u, c->d_L.as<const cx<T>>(), W0, W1);
   HIPCHK(c, hipGetLastError());
   if (mode == 2) {
     HIPCHK(c, hipFuncSetAttribute((const void*)k_grad_rr_p<T, NT, KS, NU, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((k_grad_rr_p<T, NT, KS, NU, true>), dim3(grid), dim3(256), lds, st, N, m, Nt, B, k0, nk,
-                       (const cx<T>*)c->d_A, c->d_u, (const cx<T>*)c->d_X, (const cx<T>*)c->d_L, (const cx<T>*)W0,
+                       c->d_A.as<const cx<T>>(), c->d_u, c->d_X.as<const cx<T>>(), c->d_L.as<const cx<T>>(), (const cx<T>*)W0,
                        (const cx<T>*)W1, d_dJdu, (const cx<T>*)P1, (const cx<T>*)P2);
   } else {
     HIPCHK(c, hipFuncSetAttribute((const void*)k_grad_rr_p<T, NT, KS, NU>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
     hipLaunchKernelGGL((k_grad_rr_p<T, NT, KS, NU>), dim3(grid), dim3(256), lds, st, N, m, Nt, B, k0, nk,
-                       (const cx<T>*)c->d_A, c->d_u, (const cx<T>*)c->d_X, (const cx<T>*)c->d_L, (const cx<T>*)W0,
+                       c->d_A.as<const cx<T>>(), c->d_u, c->d_X.as<const cx<T>>(), c->d_L.as<const cx<T>>(), (const cx<T>*)W0,
                        (const cx<T>*)W1, d_dJdu);
   }
   HIPCHK(c, hipGetLastError());
@@ -104,10 +104,10 @@ int grad_cap_launch(qoc_ctx* c, double* d_dJdu, hipStream_t st, int k0, int nk, 
   a.X = c->d_X;
   a.L = c->d_L;
   a.F1 = c->d_pws;
-  a.F2 = (const cx<double>*)c->d_pws + bufN;
+  a.F2 = c->d_pws.as<const cx<double>>() + bufN;
   a.G1 = c->d_gws;
-  a.G2 = (const cx<double>*)c->d_gws + bufN;
-  a.steps = (const double*)c->d_steps;
+  a.G2 = c->d_gws.as<const cx<double>>() + bufN;
+  a.steps = c->d_steps.as<const double>();
   for (int j = 0; j < 3; ++j) {
     a.mur[j] = j <= c->nu ? c->tprm.mur[j] : 0.0;
     a.mui[j] = j <= c->nu ? c->tprm.mui[j] : 0.0;
@@ -183,11 +183,7 @@ int grad_rr_exact(qoc_ctx* c, double* d_dJdu) {
     if (!c->exact_series || !c->grad_rr || c->prop_method != QOC_PROP_EXPM || blk_active(c)) return 1;
     const int N = c->N, m = c->m, Nt = c->Nt, B = c->B, nu = c->nu;
     const long long units = (long long)B * Nt;
-    if (!c->d_xn) {
-      const size_t bytes = 2 * sizeof(unsigned long long) + (size_t)units * sizeof(int);
-      HIPCHK(c, hipMalloc((void**)&c->d_xn, bytes));
-      c->dev_bytes += bytes;
-    }
+    if (!c->d_xn) HIPCHK(c, c->d_xn.alloc(2 * sizeof(unsigned long long) + (size_t)units * sizeof(int)));
     // ρ_k: the chain prep's bound of Ã_k, spectral half-widths where the Chebyshev chains apply, else 1-norms
     const bool cheb = c->chain_mode == 1 && c->cheb && tchain_mf(c);
     GradXCount cn{};
@@ -223,13 +219,7 @@ int grad_rr_exact(qoc_ctx* c, double* d_dJdu) {
     const size_t per_slice = (size_t)nmax * B * N * m * c->esz;
     const int nk_r = (int)std::max<size_t>(1, std::min<size_t>(c->xws_budget / per_slice, (size_t)Nt));
     const size_t need = per_slice * nk_r;
-    if (c->fws_bytes < need) {
-      if (c->d_fws) HIPCHK(c, hipFree(c->d_fws));
-      c->d_fws = nullptr;
-      c->fws_bytes = 0;
-      HIPCHK(c, hipMalloc(&c->d_fws, need));
-      c->fws_bytes = need;
-    }
+    HIPCHK(c, c->d_fws.grow(need));
     GradXArgs a{};
     a.N = N;
     a.m = m;

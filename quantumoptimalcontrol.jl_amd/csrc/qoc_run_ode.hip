@@ -16,8 +16,8 @@ void launch_ode_pwc(qoc_ctx* c, int adjoint, cx<T>* S, const unsigned char* pmas
   auto go = [&](auto kern) {
     hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     hipLaunchKernelGGL(kern, dim3(c->B), dim3(64 * W), lds, c->stream, N, c->m, c->nu, c->Nt, c->nsub, adjoint,
-                       (const cx<T>*)c->d_A, (const double*)c->d_u, (const cx<T>*)c->d_x0, c->x0_per_seed, S,
-                       (const cx<T>*)c->d_X, pmask, two_mu);
+                       c->d_A.as<const cx<T>>(), (const double*)c->d_u, c->d_x0.as<const cx<T>>(), c->x0_per_seed, S,
+                       c->d_X.as<const cx<T>>(), pmask, two_mu);
   };
   if (c->ode_kernel == 1) go(k_ode_pwc<T, 0>);
   else if (N <= 16) go(k_ode_pwc<T, 16>);
@@ -30,17 +30,17 @@ void launch_ode_pwc(qoc_ctx* c, int adjoint, cx<T>* S, const unsigned char* pmas
 template <typename T>
 int ode_forward(qoc_ctx* c) {
   int mk = mark_begin(c, 1);
-  launch_ode_pwc<T>(c, 0, (cx<T>*)c->d_X, nullptr, 0.0);
+  launch_ode_pwc<T>(c, 0, c->d_X.as<cx<T>>(), nullptr, 0.0);
   HIPCHK(c, hipGetLastError());
   const bool pen = c->mu != 0.0;
   if (pen) {
     hipLaunchKernelGGL((k_penalty_sum<T>), dim3(c->B), dim3(256), 0, c->stream, c->N, c->m, c->Nt,
-                       (const cx<T>*)c->d_X, c->d_pmask, c->mu, c->d_J);
+                       c->d_X.as<const cx<T>>(), c->d_pmask, c->mu, c->d_J);
     HIPCHK(c, hipGetLastError());
   }
   if (c->cost_kind != QOC_COST_EXTERNAL) {
     hipLaunchKernelGGL((k_terminal_cost<T>), dim3(c->B), dim3(256), 0, c->stream, c->N, c->m, c->Nt,
-                       (const cx<T>*)c->d_X, (const cx<T>*)c->d_Xt, c->cost_kind, c->cost_n, pen ? 1 : 0, c->d_J,
+                       c->d_X.as<const cx<T>>(), c->d_Xt.as<const cx<T>>(), c->cost_kind, c->cost_n, pen ? 1 : 0, c->d_J,
                        c->d_coef, sectors(c));
     HIPCHK(c, hipGetLastError());
   } else if (!pen) {
@@ -58,16 +58,16 @@ int ode_adjoint(qoc_ctx* c) {
   const unsigned eb = (unsigned)std::min<size_t>((Nm * B + 255) / 256, 8192);
   int mk = mark_begin(c, 2);
   if (c->cost_kind != QOC_COST_EXTERNAL) {
-    hipLaunchKernelGGL((k_lambda_final<T>), dim3(eb), dim3(256), 0, c->stream, N, m, Nt, B, (const cx<T>*)c->d_Xt,
-                       (const cx<double>*)c->d_coef, (cx<T>*)c->d_L, sectors(c));
+    hipLaunchKernelGGL((k_lambda_final<T>), dim3(eb), dim3(256), 0, c->stream, N, m, Nt, B, c->d_Xt.as<const cx<T>>(),
+                       (const cx<double>*)c->d_coef, c->d_L.as<cx<T>>(), sectors(c));
     HIPCHK(c, hipGetLastError());
   }
   if (pen) {
     hipLaunchKernelGGL((k_penalty_grad<T>), dim3(eb), dim3(256), 0, c->stream, N, m, Nt, B, Nt,
-                       (const cx<T>*)c->d_X, c->d_pmask, 2.0 * c->mu, (cx<T>*)c->d_L);
+                       c->d_X.as<const cx<T>>(), c->d_pmask, 2.0 * c->mu, c->d_L.as<cx<T>>());
     HIPCHK(c, hipGetLastError());
   }
-  launch_ode_pwc<T>(c, 1, (cx<T>*)c->d_L, pen ? c->d_pmask : nullptr, 2.0 * c->mu);
+  launch_ode_pwc<T>(c, 1, c->d_L.as<cx<T>>(), pen ? c->d_pmask : nullptr, 2.0 * c->mu);
   HIPCHK(c, hipGetLastError());
   mark_end(c, mk);
   return QOC_OK;
@@ -81,14 +81,14 @@ hipError_t launch_envelope(qoc_ctx* c, int kind, const double* dP, int np, doubl
     e = hipFuncSetAttribute((const void*)k_ode_envelope<double>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_ode_envelope<double>), dim3(c->B), dim3(64 * W), lds, c->stream, c->N, c->m, c->nu, c->Nt,
-                       kind, dP, np, dt, nsteps, (const cx<double>*)c->d_A, (const cx<double>*)c->d_x0,
-                       c->x0_per_seed, (cx<double>*)c->d_X);
+                       kind, dP, np, dt, nsteps, c->d_A.as<const cx<double>>(), c->d_x0.as<const cx<double>>(),
+                       c->x0_per_seed, c->d_X.as<cx<double>>());
   } else {
     e = hipFuncSetAttribute((const void*)k_ode_envelope<float>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL((k_ode_envelope<float>), dim3(c->B), dim3(64 * W), lds, c->stream, c->N, c->m, c->nu, c->Nt,
-                       kind, dP, np, dt, nsteps, (const cx<float>*)c->d_A, (const cx<float>*)c->d_x0,
-                       c->x0_per_seed, (cx<float>*)c->d_X);
+                       kind, dP, np, dt, nsteps, c->d_A.as<const cx<float>>(), c->d_x0.as<const cx<float>>(),
+                       c->x0_per_seed, c->d_X.as<cx<float>>());
   }
   return hipGetLastError();
 }
@@ -97,11 +97,11 @@ hipError_t launch_envelope(qoc_ctx* c, int kind, const double* dP, int np, doubl
 hipError_t launch_terminal_cost(qoc_ctx* c) {
   if (c->prec == QOC_FP64)
     hipLaunchKernelGGL((k_terminal_cost<double>), dim3(c->B), dim3(256), 0, c->stream, c->N, c->m, c->Nt,
-                       (const cx<double>*)c->d_X, (const cx<double>*)c->d_Xt, c->cost_kind, c->cost_n, 0, c->d_J,
+                       c->d_X.as<const cx<double>>(), c->d_Xt.as<const cx<double>>(), c->cost_kind, c->cost_n, 0, c->d_J,
                        c->d_coef, sectors(c));
   else
     hipLaunchKernelGGL((k_terminal_cost<float>), dim3(c->B), dim3(256), 0, c->stream, c->N, c->m, c->Nt,
-                       (const cx<float>*)c->d_X, (const cx<float>*)c->d_Xt, c->cost_kind, c->cost_n, 0, c->d_J,
+                       c->d_X.as<const cx<float>>(), c->d_Xt.as<const cx<float>>(), c->cost_kind, c->cost_n, 0, c->d_J,
                        c->d_coef, sectors(c));
   return hipGetLastError();
 }
@@ -144,13 +144,9 @@ int env_grad_plan(qoc_ctx* c, long long nsteps, EnvGradPlan* pl) {
   pl->nseg = (int)((nsteps + C - 1) / C);
   pl->lds = fixed + (size_t)pl->C * per_c;
   const size_t need = std::max<size_t>(1, (size_t)pl->nseg) * per_ckpt;
-  if (need > c->env_ws_bytes) {
+  if (need > c->d_env_ws.bytes()) {
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    if (c->d_env_ws) hipFree(c->d_env_ws);
-    c->d_env_ws = nullptr;
-    c->env_ws_bytes = 0;
-    HIPCHK(c, hipMalloc(&c->d_env_ws, need));
-    c->env_ws_bytes = need;
+    HIPCHK(c, c->d_env_ws.grow(need));
   }
   return QOC_OK;
 }
@@ -161,8 +157,8 @@ hipError_t launch_envelope_ckpt(qoc_ctx* c, int kind, const double* dP, int np, 
   hipError_t e = hipFuncSetAttribute((const void*)k_ode_envelope_ckpt, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
   if (e != hipSuccess) return e;
   hipLaunchKernelGGL(k_ode_envelope_ckpt, dim3(c->B), dim3(64 * pl.W), lds, c->stream, c->N, c->m, c->nu, c->Nt, kind,
-                     dP, np, dt, nsteps, pl.C, pl.nseg, (const cx<double>*)c->d_A, (const cx<double>*)c->d_x0,
-                     c->x0_per_seed, (cx<double>*)c->d_X, (cx<double>*)c->d_env_ws);
+                     dP, np, dt, nsteps, pl.C, pl.nseg, c->d_A.as<const cx<double>>(), c->d_x0.as<const cx<double>>(),
+                     c->x0_per_seed, c->d_X.as<cx<double>>(), c->d_env_ws.as<cx<double>>());
   return hipGetLastError();
 }
 
@@ -173,7 +169,7 @@ hipError_t launch_envelope_grad(qoc_ctx* c, int kind, const double* dP, int np, 
     hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)pl.lds);
     if (e != hipSuccess) return e;
     hipLaunchKernelGGL(kern, dim3(c->B), dim3(64 * pl.W), pl.lds, c->stream, c->N, c->m, kind, dP, np, dt, nsteps, pl.C,
-                       pl.nseg, (const cx<double>*)c->d_A, (const cx<double>*)c->d_env_ws, (const cx<double>*)c->d_Xt,
+                       pl.nseg, c->d_A.as<const cx<double>>(), c->d_env_ws.as<const cx<double>>(), c->d_Xt.as<const cx<double>>(),
                        (const cx<double>*)c->d_coef, (const cx<double>*)d_lam, d_dJdp);
     return hipGetLastError();
   };

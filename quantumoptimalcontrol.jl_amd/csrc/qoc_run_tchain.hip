@@ -123,11 +123,7 @@ bool tchain_cap_ok(const qoc_ctx* c);
 int tchain_prep(qoc_ctx* c) {
   const long long units = (long long)c->B * c->Nt;
   const bool cheb = c->cheb && tchain_mf(c);
-  if (cheb && !c->d_tcoef) {
-    const size_t bytes = (size_t)units * TCHEB_STRIDE * sizeof(double);
-    HIPCHK(c, hipMalloc((void**)&c->d_tcoef, bytes));
-    c->dev_bytes += bytes;
-  }
+  if (cheb && !c->d_tcoef) HIPCHK(c, c->d_tcoef.alloc((size_t)units * TCHEB_STRIDE * sizeof(double)));
   int mk = mark_begin(c, 0);
   const unsigned pb = (unsigned)std::min<long long>((units + 255) / 256, 2048);
   // The Chebyshev prep: one thread per unit storing its coefficient row (default), or QOC_TCHEB_PREP=1 one wave per
@@ -173,7 +169,7 @@ int tchain_forward_chain(qoc_ctx* c) {
   if (cap) {
     const size_t bufN = (size_t)c->N * ((size_t)c->B * (c->Nt + 1) * c->m);
     g.cap1 = c->d_pws;
-    g.cap2 = (cx<double>*)c->d_pws + bufN;
+    g.cap2 = c->d_pws.as<cx<double>>() + bufN;
   }
   if (tchain_mf(c)) {
     const size_t lds = tchain_mf_lds(c->N, c->m, c->nu, tchain_mf_rot(c));
@@ -224,7 +220,7 @@ int tchain_backward(qoc_ctx* c, int k_lo, int k_hi, hipStream_t st, int flags) {
     if (flags & TB_CAPTURE) {  // Q1 / Q2 of the gradient as by-products (d_gws: the W0 / W1 buffers)
       const size_t bufN = (size_t)c->N * ((size_t)c->B * (c->Nt + 1) * c->m);
       g.cap1 = c->d_gws;
-      g.cap2 = (cx<double>*)c->d_gws + bufN;
+      g.cap2 = c->d_gws.as<cx<double>>() + bufN;
     }
     g.mu_mode = (flags & TB_MU) ? 1 : 0;
     const size_t lds = tchain_mf_lds(c->N, c->m, c->nu, tchain_mf_rot(c));
@@ -290,22 +286,9 @@ int tchain_backward_overlapped(qoc_ctx* c, double* d_dJdu) {
   // light); measured: cavity (3 waves/CU) +1.3 %, zz +0.9 %, tunable bus (2 WGs x 2 waves/CU) -2.6 %
   const long long chain_waves = (long long)((c->B + c->ncu - 1) / c->ncu) * tchain_mf_waves(c->N, c->m);
   bool pre = c->bwd_prestate == 1 || (c->bwd_prestate == 2 && (chain_waves <= 3 || c->N <= 16));
-  if (pre && c->pws_bytes < pws) {  // grown on first use; without the buffer the ranges run q + p in full
-    if (c->d_pws) {
-      HIPCHK(c, hipStreamSynchronize(c->stream2));
-      HIPCHK(c, hipFree(c->d_pws));
-      c->dev_bytes -= c->pws_bytes;
-    }
-    c->d_pws = nullptr;
-    c->pws_bytes = 0;
-    if (hipMalloc(&c->d_pws, pws) == hipSuccess) {
-      c->pws_bytes = pws;
-      c->dev_bytes += pws;
-    } else {
-      (void)hipGetLastError();
-      c->d_pws = nullptr;
-      pre = false;
-    }
+  if (pre && c->d_pws.bytes() < pws) {  // grown on first use; without the buffer the ranges run q + p in full
+    if (c->d_pws) HIPCHK(c, hipStreamSynchronize(c->stream2));
+    if (c->d_pws.grow(pws) != hipSuccess) pre = false;
   }
   HIPCHK(c, hipEventRecord(c->sync_ev[S], c->stream));  // stream2 starts after everything queued so far
   HIPCHK(c, hipStreamWaitEvent(c->stream2, c->sync_ev[S], 0));
@@ -343,10 +326,10 @@ hipError_t launch_pade_units(qoc_ctx* c, long long units) {
   const unsigned blocks = (unsigned)std::min<long long>((units + 3) / 4, 8192);
   if (c->prec == QOC_FP64)
     hipLaunchKernelGGL((k_pade_units<double>), dim3(blocks), dim3(256), 0, c->stream, c->N, c->nu, units,
-                       (const cx<double>*)c->d_A, (const double*)c->d_u, c->d_hist);
+                       c->d_A.as<const cx<double>>(), (const double*)c->d_u, c->d_hist);
   else
     hipLaunchKernelGGL((k_pade_units<float>), dim3(blocks), dim3(256), 0, c->stream, c->N, c->nu, units,
-                       (const cx<float>*)c->d_A, (const double*)c->d_u, c->d_hist);
+                       c->d_A.as<const cx<float>>(), (const double*)c->d_u, c->d_hist);
   return hipGetLastError();
 }
 
@@ -360,22 +343,12 @@ bool tchain_cap_ok(const qoc_ctx* c) {
 // d_pws: the forward captures (two state-shaped buffers), grown on first use; QOC_ERR_HIP if it cannot be had
 int ensure_pws(qoc_ctx* c) {
   const size_t pws = (size_t)2 * c->N * c->B * (c->Nt + 1) * c->m * c->esz;
-  if (c->d_pws && c->pws_bytes >= pws) return QOC_OK;
+  if (c->d_pws.bytes() >= pws) return QOC_OK;
   if (c->d_pws) {
     if (c->stream2) HIPCHK(c, hipStreamSynchronize(c->stream2));
     HIPCHK(c, hipStreamSynchronize(c->stream));
-    HIPCHK(c, hipFree(c->d_pws));
-    c->dev_bytes -= c->pws_bytes;
   }
-  c->d_pws = nullptr;
-  c->pws_bytes = 0;
-  if (hipMalloc(&c->d_pws, pws) != hipSuccess) {
-    (void)hipGetLastError();
-    c->d_pws = nullptr;
-    return fail(c, QOC_ERR_HIP, "capture buffers (%zu bytes) not available", pws);
-  }
-  c->pws_bytes = pws;
-  c->dev_bytes += pws;
+  if (c->d_pws.grow(pws) != hipSuccess) return fail(c, QOC_ERR_HIP, "capture buffers (%zu bytes) not available", pws);
   return QOC_OK;
 }
 
@@ -445,10 +418,7 @@ int tchain_eval_concurrent(qoc_ctx* c, double* d_dJdu) {
   int r = ensure_stream2(c, 4);
   if (r) return r;
   if ((r = ensure_pws(c))) return r;
-  if (!c->d_coef_mu) {
-    HIPCHK(c, hipMalloc((void**)&c->d_coef_mu, (size_t)c->B * 2 * c->m_user * sizeof(cx<double>)));
-    c->dev_bytes += (size_t)c->B * 2 * c->m_user * sizeof(cx<double>);
-  }
+  if (!c->d_coef_mu) HIPCHK(c, c->d_coef_mu.alloc((size_t)c->B * 2 * c->m_user * sizeof(cx<double>)));
   // the step records first (both chains read them)
   if ((r = tchain_prep(c))) return r;
   HIPCHK(c, hipEventRecord(c->sync_ev[0], c->stream));
@@ -467,9 +437,9 @@ int tchain_eval_concurrent(qoc_ctx* c, double* d_dJdu) {
     const size_t bufN = (size_t)c->N * ((size_t)c->B * (c->Nt + 1) * c->m);
     TChainArgs gf = tchain_args(c), gb = tchain_args(c);
     gf.cap1 = c->d_pws;
-    gf.cap2 = (cx<double>*)c->d_pws + bufN;
+    gf.cap2 = c->d_pws.as<cx<double>>() + bufN;
     gb.cap1 = c->d_gws;
-    gb.cap2 = (cx<double>*)c->d_gws + bufN;
+    gb.cap2 = c->d_gws.as<cx<double>>() + bufN;
     gb.mu_mode = 1;
     const size_t lds = tchain_mf_lds(c->N, c->m, c->nu, tchain_mf_rot(c));
     const int threads = tchain_mf_threads(c);
