@@ -495,6 +495,36 @@ int qoc_opt_tell_dev(qoc_opt* opt, void* stream, const double* d_f, const double
  * ticks_out: the ticks the slowest seed used.  QOC_ERR_STATE without a spline basis, QOC_ERR_ARG when B or n differ. */
 int qoc_minimize_spline_dev(qoc_ctx* ctx, qoc_opt* opt, double* d_c, long long max_ticks, int poll_every,
                             long long* ticks_out);
+/* The duration form: every seed's variables are z_b = [c_b (ns * nu values, index s + ns * j), tau_b], the gate
+ * duration of qoc_set_time_scale as the last of n = ns * nu + 1 <= 256 variables, for time-optimal control
+ * (minimise f = J + time_weight * tau).  lower / upper of params bound c; tau has tau_lower / tau_upper of its own; the
+ * two spline norms and their Jacobians run over c only; the L-BFGS recursion, the line search and the gtol test run
+ * over all n variables.
+ * qoc_opt_create_duration: params->n == ns * nu + 1 when ns, nu > 0; with ns = nu = 0 the last of the n variables is the
+ *   one with its own bounds and there are no constraints.  tau_lower finite and > 0, tau_lower <= tau_upper (+inf
+ *   allowed), time_weight finite: QOC_ERR_ARG otherwise; QOC_ERR_UNSUPPORTED for n > 256 or memory > 16; all checked
+ *   before the GPU is touched.  qoc_opt_start_dev, qoc_opt_tell_dev, qoc_opt_trial_dev, qoc_opt_field_dev and
+ *   qoc_opt_result work on the object as on a plain one.  In ask / tell the caller's f and grad are complete:
+ *   time_weight is used by qoc_minimize_spline_duration_dev only.
+ * qoc_minimize_spline_duration_dev: qoc_minimize_spline_dev for such an object, with the same grouping, polling,
+ *   max_ticks = 0 behaviour and closing eval.  Per tick one eval under the time scale and one fused step kernel:
+ *   grad = [Bs' dJdu', dJ/dtau + time_weight], f = J + time_weight * tau (a product, then a sum), the seed's state
+ *   machine, then u = transpose(Bs c) and tau of its next trial written into the context's controls and time-scale
+ *   buffer.  d_z (B x (ns * nu + 1), device): the starts in, the final iterates out.  QOC_OPT_F and the result's f are
+ *   J + time_weight * tau at the iterate.  The context's best (J, seed) (qoc_allgather_best) is the closing eval's own:
+ *   the minimum of J, not of f.  What the call leaves on the context is what qoc_minimize_spline_dev leaves under a
+ *   time scale.
+ *   Requires qoc_set_time_scale to have been made (any values: the call overwrites all B; on return the buffer holds
+ *   the final tau).  QOC_ERR_STATE: no spline basis, no time scale, QOC_COST_EXTERNAL.  QOC_ERR_ARG: an object made by
+ *   qoc_opt_create (and a duration object passed to qoc_minimize_spline_dev); B, device or n differ.  Everything an
+ *   eval under a time scale refuses (QOC_ERR_UNSUPPORTED, see qoc_set_time_scale) is refused before anything changes:
+ *   d_z, the time-scale buffer, the context's controls and J are as they were. */
+typedef struct qoc_opt_duration {
+  double tau_lower, tau_upper, time_weight;
+} qoc_opt_duration;
+int qoc_opt_create_duration(qoc_opt** out, int device, int B, const qoc_opt_params* params, const qoc_opt_duration* dur);
+int qoc_minimize_spline_duration_dev(qoc_ctx* ctx, qoc_opt* opt, double* d_z, long long max_ticks, int poll_every,
+                                     long long* ticks_out);
 /* Device pointers of the per-seed results (valid for the object's life; read them after the stream has drained). */
 #define QOC_OPT_X 0          /* B x n doubles: iterates */
 #define QOC_OPT_F 1          /* B doubles: objective at the iterate (without constraint terms) */

@@ -2044,17 +2044,26 @@ int qoc_expm_jacobian(int device, int N, int nu, const double* A0, const double*
 
 // ---- device-resident multi-start optimiser (qoc_opt.hpp) ----
 
-int qoc_opt_create(qoc_opt** out, int device, int B, const qoc_opt_params* p) {
+// qoc_opt_create and qoc_opt_create_duration (dur != nullptr: n = ns * nu + 1, the last variable with dur's bounds)
+static int opt_create(qoc_opt** out, int device, int B, const qoc_opt_params* p, const qoc_opt_duration* dur) {
   if (!out || !p) return fail(nullptr, QOC_ERR_ARG, "null argument");
   *out = nullptr;
+  const int nd = dur ? 1 : 0;
   if (B < 1 || p->n < 1 || p->memory < 1 || p->max_ls < 1 || p->max_iter < 0)
     return fail(nullptr, QOC_ERR_ARG, "invalid optimiser dimensions (B=%d n=%d memory=%d max_ls=%d max_iter=%d)", B, p->n,
                 p->memory, p->max_ls, p->max_iter);
   if (p->n > OPT_MAX_N || p->memory > OPT_MAX_MEM)
     return fail(nullptr, QOC_ERR_UNSUPPORTED, "the device optimiser takes n <= %d and memory <= %d (got n=%d memory=%d)",
                 OPT_MAX_N, OPT_MAX_MEM, p->n, p->memory);
-  if (p->ns < 0 || p->nu < 0 || ((p->ns > 0 || p->nu > 0) && (long long)p->ns * p->nu != p->n))
-    return fail(nullptr, QOC_ERR_ARG, "constraints need n == ns * nu (n=%d ns=%d nu=%d)", p->n, p->ns, p->nu);
+  if (p->ns < 0 || p->nu < 0 || ((p->ns > 0 || p->nu > 0) && (long long)p->ns * p->nu + nd != p->n))
+    return fail(nullptr, QOC_ERR_ARG, "constraints need n == ns * nu%s (n=%d ns=%d nu=%d)", dur ? " + 1" : "", p->n, p->ns,
+                p->nu);
+  if (dur) {
+    if (!std::isfinite(dur->tau_lower) || !(dur->tau_lower > 0.0) || !(dur->tau_lower <= dur->tau_upper))
+      return fail(nullptr, QOC_ERR_ARG, "the duration needs 0 < tau_lower <= tau_upper, tau_lower finite (got %g, %g)",
+                  dur->tau_lower, dur->tau_upper);
+    if (!std::isfinite(dur->time_weight)) return fail(nullptr, QOC_ERR_ARG, "time_weight must be finite");
+  }
   if (!(p->lower <= p->upper)) return fail(nullptr, QOC_ERR_ARG, "lower bound above upper bound");
   if (p->ns > 0 && !(p->rho0 > 0.0)) return fail(nullptr, QOC_ERR_ARG, "rho0 must be positive");
   HIPCHK(nullptr, hipSetDevice(device));
@@ -2064,6 +2073,10 @@ int qoc_opt_create(qoc_opt** out, int device, int B, const qoc_opt_params* p) {
   o->order = p->order;
   o->P = OptParams{p->n, p->ns, p->nu, p->max_iter, p->memory, p->outer_iters, p->max_ls, p->lower, p->upper,
                    p->g_upper[0], p->g_upper[1], p->rho0, p->gtol};
+  if (dur) {
+    o->dur = true;
+    o->D = OptDur{dur->tau_lower, dur->tau_upper, dur->time_weight};
+  }
   bool ok = true;
   auto alloc = [&](size_t bytes) -> void* {
     void* q = nullptr;
@@ -2109,6 +2122,15 @@ int qoc_opt_create(qoc_opt** out, int device, int B, const qoc_opt_params* p) {
   return QOC_OK;
 }
 
+int qoc_opt_create(qoc_opt** out, int device, int B, const qoc_opt_params* p) {
+  return opt_create(out, device, B, p, nullptr);
+}
+
+int qoc_opt_create_duration(qoc_opt** out, int device, int B, const qoc_opt_params* p, const qoc_opt_duration* dur) {
+  if (!dur) return fail(nullptr, QOC_ERR_ARG, "null argument");
+  return opt_create(out, device, B, p, dur);
+}
+
 void qoc_opt_destroy(qoc_opt* o) {
   if (!o) return;
   hipSetDevice(o->dev);
@@ -2123,8 +2145,11 @@ int qoc_opt_start_dev(qoc_opt* o, void* stream, const double* d_c0) {
   if (!o || !d_c0) return fail(nullptr, QOC_ERR_ARG, "null argument");
   HIPCHK(nullptr, hipSetDevice(o->dev));
   const long long total = (long long)o->B * o->P.n;
-  hipLaunchKernelGGL(k_opt_start, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream, o->B, o->P,
-                     o->st, d_c0);
+  const dim3 grid((unsigned)((total + 255) / 256));
+  if (o->dur)
+    hipLaunchKernelGGL(k_opt_start_dur, grid, dim3(256), 0, (hipStream_t)stream, o->B, o->P, o->D, o->st, d_c0);
+  else
+    hipLaunchKernelGGL(k_opt_start, grid, dim3(256), 0, (hipStream_t)stream, o->B, o->P, o->st, d_c0);
   HIPCHK(nullptr, hipGetLastError());
   return QOC_OK;
 }
@@ -2134,8 +2159,11 @@ double* qoc_opt_trial_dev(qoc_opt* o) { return o ? o->st.xt : nullptr; }
 int qoc_opt_tell_dev(qoc_opt* o, void* stream, const double* d_f, const double* d_grad) {
   if (!o || !d_f || !d_grad) return fail(nullptr, QOC_ERR_ARG, "null argument");
   HIPCHK(nullptr, hipSetDevice(o->dev));
-  hipLaunchKernelGGL(k_opt_tell, dim3((unsigned)((o->B + 3) / 4)), dim3(256), 0, (hipStream_t)stream, o->B, o->P, o->st,
-                     d_f, d_grad);
+  const dim3 grid((unsigned)((o->B + 3) / 4));
+  if (o->dur)
+    hipLaunchKernelGGL(k_opt_tell_dur, grid, dim3(256), 0, (hipStream_t)stream, o->B, o->P, o->D, o->st, d_f, d_grad);
+  else
+    hipLaunchKernelGGL(k_opt_tell, grid, dim3(256), 0, (hipStream_t)stream, o->B, o->P, o->st, d_f, d_grad);
   HIPCHK(nullptr, hipGetLastError());
   return QOC_OK;
 }
@@ -2193,6 +2221,8 @@ int qoc_minimize_spline_dev(qoc_ctx* c, qoc_opt* o, double* d_c, long long max_t
   if (o->B != c->B || o->dev != c->dev)
     return fail(c, QOC_ERR_ARG, "the optimiser has B=%d on device %d, the context B=%d on device %d", o->B, o->dev, c->B,
                 c->dev);
+  if (o->dur)
+    return fail(c, QOC_ERR_ARG, "the optimiser was made by qoc_opt_create_duration: qoc_minimize_spline_duration_dev runs it");
   if (o->P.ns != c->ns || o->P.nu != c->nu || o->P.n != c->ns * c->nu)
     return fail(c, QOC_ERR_ARG, "the optimiser has n=%d (ns=%d, nu=%d), the context ns=%d, nu=%d", o->P.n, o->P.ns,
                 o->P.nu, c->ns, c->nu);
@@ -2230,6 +2260,73 @@ int qoc_minimize_spline_dev(qoc_ctx* c, qoc_opt* o, double* d_c, long long max_t
   if (ticks == 0)
     HIPCHK(c, hipMemcpyAsync(o->st.f, c->d_J, (size_t)c->B * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   HIPCHK(c, hipMemcpyAsync(d_c, o->st.x, (size_t)c->B * o->P.n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
+  std::vector<int> ev(c->B);
+  HIPCHK(c, hipMemcpyAsync(ev.data(), o->st.evals, (size_t)c->B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+  HIPCHK(c, hipStreamSynchronize(c->stream));
+  if (ticks_out) *ticks_out = *std::max_element(ev.begin(), ev.end());
+  return QOC_OK;
+}
+
+int qoc_minimize_spline_duration_dev(qoc_ctx* c, qoc_opt* o, double* d_z, long long max_ticks, int poll_every,
+                                     long long* ticks_out) {
+  if (!c) return fail(nullptr, QOC_ERR_ARG, "null context");
+  if (!o || !d_z) return fail(c, QOC_ERR_ARG, "null argument");
+  if (!c->ns) return fail(c, QOC_ERR_STATE, "spline basis not set (qoc_set_spline_basis)");
+  if (!o->dur)
+    return fail(c, QOC_ERR_ARG, "the optimiser was made by qoc_opt_create: qoc_opt_create_duration makes the duration form");
+  if (o->B != c->B || o->dev != c->dev)
+    return fail(c, QOC_ERR_ARG, "the optimiser has B=%d on device %d, the context B=%d on device %d", o->B, o->dev, c->B,
+                c->dev);
+  if (o->P.ns != c->ns || o->P.nu != c->nu || o->P.n != c->ns * c->nu + 1)
+    return fail(c, QOC_ERR_ARG, "the optimiser has n=%d (ns=%d, nu=%d), the context ns=%d, nu=%d", o->P.n, o->P.ns,
+                o->P.nu, c->ns, c->nu);
+  if (max_ticks < 0) return fail(c, QOC_ERR_ARG, "max_ticks must be >= 0");
+  if (!c->ts_on)
+    return fail(c, QOC_ERR_STATE, "qoc_minimize_spline_duration_dev needs a time scale (qoc_set_time_scale): it writes "
+                                  "the seeds' durations into that buffer");
+  if (c->cost_kind == QOC_COST_EXTERNAL)
+    return fail(c, QOC_ERR_STATE, "qoc_minimize_spline_duration_dev needs a device-side cost (TRACE or ZCAL)");
+  int r = check_ready(c);
+  if (r) return r;
+  // what the evals under the time scale would refuse is refused here, before the start overwrites u and tau
+  const int order = o->order;
+  if ((r = ts_eval_check(c, order))) return r;
+  if (poll_every <= 0) poll_every = 16;
+  if ((r = qoc_opt_start_dev(o, c->stream, d_z))) return fail(c, r, "%s", g_err.c_str());
+  const long long nuT = (long long)c->B * c->Nt * c->nu;
+  const unsigned blocks = (unsigned)std::min<long long>((nuT + 255) / 256, 4096);
+  double* const d_tau = c->d_ts;
+  const double* const d_dtau = c->d_ts + c->B;
+  hipLaunchKernelGGL(k_spline_u_tau, dim3(blocks), dim3(256), 0, c->stream, c->B, c->Nt, c->ns, c->nu,
+                     (const double*)c->d_Bs, (const double*)o->st.xt, c->d_u, d_tau);
+  HIPCHK(c, hipGetLastError());
+  long long ticks = 0;
+  while (ticks < max_ticks) {
+    const long long group = std::min<long long>(poll_every, max_ticks - ticks);
+    for (long long t = 0; t < group; ++t) {
+      // the eval on the context's own controls and time scale, then the seeds' steps, which write the next trials' there
+      if ((r = qoc_eval_dev(c, c->d_u, order, c->d_J, c->d_dJdu))) return r;
+      hipLaunchKernelGGL(k_opt_step_spline_dur, dim3(c->B), dim3(256), 0, c->stream, o->P, o->D, o->st, c->Nt,
+                         (const double*)c->d_Bs, (const double*)c->d_dJdu, (const double*)c->d_J, d_dtau, c->d_u, d_tau);
+      HIPCHK(c, hipGetLastError());
+    }
+    ticks += group;
+    HIPCHK(c, hipEventRecord(o->ev, c->stream));
+    HIPCHK(c, hipEventSynchronize(o->ev));
+    if (*(volatile int*)o->h_done >= o->B) break;
+  }
+  // closing eval at the final iterates: u, tau, J and the best-(J, seed) epilogue are the result's
+  hipLaunchKernelGGL(k_spline_u_tau, dim3(blocks), dim3(256), 0, c->stream, c->B, c->Nt, c->ns, c->nu,
+                     (const double*)c->d_Bs, (const double*)o->st.x, c->d_u, d_tau);
+  HIPCHK(c, hipGetLastError());
+  if ((r = qoc_eval_dev(c, c->d_u, order, c->d_J, nullptr))) return r;
+  // no tick ran (max_ticks = 0): no seed has taken an eval, so the result's f is the closing eval's J + kappa tau
+  if (ticks == 0) {
+    hipLaunchKernelGGL(k_opt_f_dur, dim3((unsigned)((c->B + 255) / 256)), dim3(256), 0, c->stream, c->B, o->P.n, o->D.kappa,
+                       (const double*)c->d_J, (const double*)o->st.x, o->st.f);
+    HIPCHK(c, hipGetLastError());
+  }
+  HIPCHK(c, hipMemcpyAsync(d_z, o->st.x, (size_t)c->B * o->P.n * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
   std::vector<int> ev(c->B);
   HIPCHK(c, hipMemcpyAsync(ev.data(), o->st.evals, (size_t)c->B * sizeof(int), hipMemcpyDeviceToHost, c->stream));
   HIPCHK(c, hipStreamSynchronize(c->stream));

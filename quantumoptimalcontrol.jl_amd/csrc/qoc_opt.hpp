@@ -29,6 +29,12 @@ struct OptParams {
   double lower, upper, gu0, gu1, rho0, gtol;
 };
 
+// the duration form (qoc_opt_create_duration): the last variable is a gate duration τ with bounds of its own; kappa is
+// the weight of τ in f = J + kappa τ, used by the fused step only
+struct OptDur {
+  double tau_lo, tau_hi, kappa;
+};
+
 struct OptState {
   double *x, *gx, *d, *xt;  // B x n: iterate, merit gradient there, direction, trial
   double *S, *Y;            // B x memory x n
@@ -66,10 +72,23 @@ __device__ __forceinline__ void opt_mirror_done(const OptState& st) {
 
 // One tick of seed b, run by one full wave.  f_in, grad[0..n): the objective and its gradient at the seed's trial
 // st.xt; the next trial is written to st.xt (and to xt_out when given, e.g. LDS).  A DONE seed returns at once.
+// DUR: variable n - 1 is the duration: clamped to [D.tau_lo, D.tau_hi] instead of the scalar bounds and left out of
+// the two spline norms and their Jacobians (n - 1 = ns nu would read as s = 0, j = nu); everything else runs over all n.
+template <bool DUR = false>
 __device__ __forceinline__ void opt_tell(const OptParams& P, const OptState& st, int b, int lane, double f_in,
-                                         const double* grad, double* xt_out) {
+                                         const double* grad, double* xt_out, const OptDur D = OptDur{}) {
 #pragma clang fp contract(off)
   const int n = P.n, m = P.memory;
+  const int nc = DUR ? n - 1 : n;  // variables the spline norms run over
+  // bounds of the variable in register row r of this lane
+  auto lo_of = [&](int r) -> double {
+    if constexpr (DUR) return lane + WAVE * r == nc ? D.tau_lo : P.lower;
+    return P.lower;
+  };
+  auto hi_of = [&](int r) -> double {
+    if constexpr (DUR) return lane + WAVE * r == nc ? D.tau_hi : P.upper;
+    return P.upper;
+  };
   int* ir = st.irec + (size_t)b * OI_STRIDE;
   double* dr = st.rec + (size_t)b * OD_STRIDE;
   const int phase = ir[OI_PHASE];
@@ -103,15 +122,17 @@ __device__ __forceinline__ void opt_tell(const OptParams& P, const OptState& st,
   const double lam0 = cons ? st.lam[2 * b] : 0.0, lam1 = cons ? st.lam[2 * b + 1] : 0.0, rho = cons ? st.rho[b] : 0.0;
   if (cons) {
     const int ns = P.ns;
-    double dl[OPT_R], dq[OPT_R];
+    double dl[OPT_R], dq[OPT_R], xc[OPT_R];
     double s0 = 0.0, s1 = 0.0;
 #pragma unroll
     for (int r = 0; r < OPT_R; ++r) {
       const int i = lane + WAVE * r;
       const int s = i % ns;
-      dl[r] = (i < n && s > 0) ? xt[r] - xtb[i - 1] : 0.0;
-      dq[r] = (i < n && s + 1 < ns) ? xtb[i + 1] - xt[r] : 0.0;
-      s0 = fma(xt[r], xt[r], s0);
+      if constexpr (DUR) xc[r] = i < nc ? xt[r] : 0.0;
+      else xc[r] = xt[r];
+      dl[r] = (i < nc && s > 0) ? xt[r] - xtb[i - 1] : 0.0;
+      dq[r] = (i < nc && s + 1 < ns) ? xtb[i + 1] - xt[r] : 0.0;
+      s0 = fma(xc[r], xc[r], s0);
       s1 = fma(dl[r], dl[r], s1);
     }
     g0 = sqrt(opt_wave_sum(s0));
@@ -121,7 +142,7 @@ __device__ __forceinline__ void opt_tell(const OptParams& P, const OptState& st,
     phi = f_in + ((a0 * a0 - lam0 * lam0) + (a1 * a1 - lam1 * lam1)) / (2.0 * rho);
 #pragma unroll
     for (int r = 0; r < OPT_R; ++r) {
-      const double j0 = g0 > 0.0 ? xt[r] / g0 : 0.0;
+      const double j0 = g0 > 0.0 ? xc[r] / g0 : 0.0;
       const double j1 = g1 > 0.0 ? (dl[r] - dq[r]) / g1 : 0.0;
       gp[r] = gp[r] + (a0 * j0 + a1 * j1);
     }
@@ -199,7 +220,7 @@ __device__ __forceinline__ void opt_tell(const OptParams& P, const OptState& st,
       } else {
         alpha = alpha * 0.5;
 #pragma unroll
-        for (int r = 0; r < OPT_R; ++r) xt[r] = opt_clamp(x[r] + alpha * dv[r], P.lower, P.upper);
+        for (int r = 0; r < OPT_R; ++r) xt[r] = opt_clamp(x[r] + alpha * dv[r], lo_of(r), hi_of(r));
       }
     }
   }
@@ -230,7 +251,7 @@ __device__ __forceinline__ void opt_tell(const OptParams& P, const OptState& st,
     if (!end_round) {
 #pragma unroll
       for (int r = 0; r < OPT_R; ++r) {
-        fr[r] = !((x[r] <= P.lower && gx[r] > 0.0) || (x[r] >= P.upper && gx[r] < 0.0));
+        fr[r] = !((x[r] <= lo_of(r) && gx[r] > 0.0) || (x[r] >= hi_of(r) && gx[r] < 0.0));
         q[r] = fr[r] ? gx[r] : 0.0;
         pgn = fmax(pgn, fabs(q[r]));
       }
@@ -305,7 +326,7 @@ __device__ __forceinline__ void opt_tell(const OptParams& P, const OptState& st,
       for (int r = 0; r < OPT_R; ++r) {
         const int i = lane + WAVE * r;
         if (i < n) db[i] = d[r];
-        xt[r] = opt_clamp(x[r] + alpha * d[r], P.lower, P.upper);
+        xt[r] = opt_clamp(x[r] + alpha * d[r], lo_of(r), hi_of(r));
       }
     } else {
       // end of the round: the trial goes back to x
@@ -355,7 +376,9 @@ __device__ __forceinline__ void opt_tell(const OptParams& P, const OptState& st,
 }
 
 // x = xt = clamp(c0), every seed in INIT with zero multipliers and counters
-static __global__ void k_opt_start(int B, OptParams P, OptState st, const double* __restrict__ c0) {
+template <bool DUR>
+__device__ __forceinline__ void opt_start(int B, const OptParams& P, const OptState& st, const double* __restrict__ c0,
+                                          const OptDur D = OptDur{}) {
   const long long total = (long long)B * P.n;
   const long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x;
   if (g == 0) {
@@ -363,7 +386,11 @@ static __global__ void k_opt_start(int B, OptParams P, OptState st, const double
     __hip_atomic_store(st.host_done, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
   }
   if (g >= total) return;
-  const double v = opt_clamp(c0[g], P.lower, P.upper);
+  double v;
+  if constexpr (DUR)
+    v = g % P.n == P.n - 1 ? opt_clamp(c0[g], D.tau_lo, D.tau_hi) : opt_clamp(c0[g], P.lower, P.upper);
+  else
+    v = opt_clamp(c0[g], P.lower, P.upper);
   st.x[g] = v;
   st.xt[g] = v;
   st.gx[g] = 0.0;
@@ -379,6 +406,12 @@ static __global__ void k_opt_start(int B, OptParams P, OptState st, const double
     st.evals[b] = st.iters[b] = st.rounds[b] = st.converged[b] = st.done[b] = st.fails[b] = 0;
   }
 }
+static __global__ void k_opt_start(int B, OptParams P, OptState st, const double* __restrict__ c0) {
+  opt_start<false>(B, P, st, c0);
+}
+static __global__ void k_opt_start_dur(int B, OptParams P, OptDur D, OptState st, const double* __restrict__ z0) {
+  opt_start<true>(B, P, st, z0, D);
+}
 
 // generic ask/tell step: four seeds per workgroup, one wave each
 static __global__ __launch_bounds__(256) void k_opt_tell(int B, OptParams P, OptState st, const double* f,
@@ -387,6 +420,14 @@ static __global__ __launch_bounds__(256) void k_opt_tell(int B, OptParams P, Opt
   const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
   if (b >= B) return;
   opt_tell(P, st, b, threadIdx.x & 63, f[b], grad + (size_t)b * P.n, nullptr);
+}
+// the same with the last variable a duration; the caller's f and grad are complete (D.kappa is not used)
+static __global__ __launch_bounds__(256) void k_opt_tell_dur(int B, OptParams P, OptDur D, OptState st, const double* f,
+                                                             const double* grad) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) opt_mirror_done(st);
+  const int b = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (b >= B) return;
+  opt_tell<true>(P, st, b, threadIdx.x & 63, f[b], grad + (size_t)b * P.n, nullptr, D);
 }
 
 // the fused per-tick step of the spline form, one workgroup per seed: dJdc = Bs' dJdu' in k_spline_grad's summation
@@ -437,11 +478,96 @@ static __global__ __launch_bounds__(256) void k_opt_step_spline(OptParams P, Opt
   }
 }
 
+// the fused per-tick step of the duration form, z_b = [c_b, τ_b] with rows of stride n = ns nu + 1: k_opt_step_spline
+// with the gradient's last entry dJ/dτ + kappa, the objective J + kappa τ at the trial's τ (a product, then a sum: the
+// bits of torch's J + kappa * tau), and the next trial's τ written into the context's time-scale buffer beside its u
+static __global__ __launch_bounds__(256) void k_opt_step_spline_dur(OptParams P, OptDur D, OptState st, int Nt,
+                                                                    const double* __restrict__ Bs,
+                                                                    const double* __restrict__ dJdu,
+                                                                    const double* __restrict__ J,
+                                                                    const double* __restrict__ dJdtau,
+                                                                    double* __restrict__ u, double* __restrict__ tau) {
+#pragma clang fp contract(off)
+  __shared__ double s_g[OPT_MAX_N], s_xt[OPT_MAX_N];
+  const int b = blockIdx.x, ns = P.ns, nu = P.nu, nc = P.n - 1;
+  if (b == 0 && threadIdx.x == 0) opt_mirror_done(st);
+  if (st.irec[(size_t)b * OI_STRIDE + OI_PHASE] == OPT_DONE) return;
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const double* gb = dJdu + (size_t)b * nu * Nt;
+  for (int o0 = wave; o0 < nc; o0 += 16) {
+    double acc[4] = {0.0, 0.0, 0.0, 0.0};
+    const double* bp[4];
+    const double* gp4[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const int o = o0 + 4 * q < nc ? o0 + 4 * q : o0;  // a slot past the end repeats the first (not stored)
+      bp[q] = Bs + (size_t)Nt * (o % ns);
+      gp4[q] = gb + o / ns;
+    }
+    for (int k = lane; k < Nt; k += 64) {
+#pragma unroll
+      for (int q = 0; q < 4; ++q) acc[q] = fma(bp[q][k], gp4[q][(size_t)k * nu], acc[q]);
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+      const double v = opt_wave_sum(acc[q]);
+      if (lane == 0 && o0 + 4 * q < nc) s_g[o0 + 4 * q] = v;
+    }
+  }
+  if (threadIdx.x == 0) s_g[nc] = dJdtau[b] + D.kappa;
+  __syncthreads();
+  if (wave == 0) {
+    const double kt = D.kappa * st.xt[(size_t)b * P.n + nc];
+    opt_tell<true>(P, st, b, lane, J[b] + kt, s_g, s_xt, D);
+  }
+  __syncthreads();
+  double* ub = u + (size_t)b * nu * Nt;
+  for (int e = threadIdx.x; e < Nt * nu; e += 256) {
+    const int j = e % nu, k = e / nu;
+    double acc = 0.0;
+    for (int s = 0; s < ns; ++s) acc = fma(Bs[k + (size_t)Nt * s], s_xt[s + ns * j], acc);
+    ub[e] = acc;
+  }
+  if (threadIdx.x == 0) tau[b] = s_xt[nc];
+}
+
+// u = transpose(Bs c_b) in k_spline_u's order and tau[b] = z[b n + ns nu] from rows z_b = [c_b, τ_b] of stride
+// n = ns nu + 1: the controls and time scale of the duration form's start and closing eval
+static __global__ void k_spline_u_tau(int B, int Nt, int ns, int nu, const double* __restrict__ Bs,
+                                      const double* __restrict__ z, double* __restrict__ u, double* __restrict__ tau) {
+#pragma clang fp contract(off)
+  const long long total = (long long)B * Nt * nu;
+  const int n = ns * nu + 1;
+  for (long long g = blockIdx.x * (long long)blockDim.x + threadIdx.x; g < total; g += (long long)gridDim.x * blockDim.x) {
+    const int j = (int)(g % nu);
+    const long long bk = g / nu;
+    const int k = (int)(bk % Nt);
+    const int b = (int)(bk / Nt);
+    const double* cb = z + (size_t)b * n + (size_t)ns * j;
+    double acc = 0.0;
+    for (int s = 0; s < ns; ++s) acc = fma(Bs[k + (size_t)Nt * s], cb[s], acc);
+    u[g] = acc;
+    if (j == 0 && k == 0) tau[b] = z[(size_t)b * n + n - 1];
+  }
+}
+
+// f_b = J_b + kappa τ_b at the iterates, for a run in which no seed took an eval (max_ticks = 0)
+static __global__ void k_opt_f_dur(int B, int n, double kappa, const double* __restrict__ J, const double* __restrict__ x,
+                                   double* __restrict__ f) {
+#pragma clang fp contract(off)
+  const int b = blockIdx.x * blockDim.x + threadIdx.x;
+  if (b >= B) return;
+  const double kt = kappa * x[(size_t)b * n + n - 1];
+  f[b] = J[b] + kt;
+}
+
 }  // namespace qoc
 
 // host object behind qoc_opt (include/qoc.h)
 struct qoc_opt {
   int dev = 0, B = 0, order = 3;
+  bool dur = false;  // qoc_opt_create_duration: the last variable is a duration with the bounds in D
+  qoc::OptDur D{};
   qoc::OptParams P{};
   qoc::OptState st{};
   int* h_done = nullptr;  // host-mapped word behind st.host_done

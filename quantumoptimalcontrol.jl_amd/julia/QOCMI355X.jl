@@ -209,6 +209,50 @@ callers that write τ on the library's stream between evals; not run, see above.
 time_scale_device(c::MI355XCache) = ccall((:qoc_time_scale_dev, libqoc), Ptr{Cdouble}, (Ptr{Cvoid},), c.ctx)
 time_scale_grad_device(c::MI355XCache) = ccall((:qoc_time_scale_grad_dev, libqoc), Ptr{Cdouble}, (Ptr{Cvoid},), c.ctx)
 
+# qoc_opt_params and qoc_opt_duration (include/qoc.h), field for field
+struct OptParams
+    n::Cint; ns::Cint; nu::Cint
+    lower::Cdouble; upper::Cdouble
+    g_upper::NTuple{2,Cdouble}
+    max_iter::Cint; memory::Cint; outer_iters::Cint; max_ls::Cint
+    rho0::Cdouble; gtol::Cdouble
+    order::Cint
+end
+struct OptDuration
+    tau_lower::Cdouble; tau_upper::Cdouble; time_weight::Cdouble
+end
+
+"""
+    opt_create_duration(B, params::OptParams, dur::OptDuration; device=0) -> Ptr{Cvoid}
+
+The device optimiser with the gate duration as every seed's last variable (`qoc_opt_create_duration`): z = [c, τ],
+`params.n == ns * nu + 1`, `params.lower / upper` bound c and `dur.tau_lower / tau_upper` bound τ.  Free the handle with
+`ccall((:qoc_opt_destroy, libqoc), Cvoid, (Ptr{Cvoid},), opt)`.  Not run, see `set_time_scale!`.
+"""
+function opt_create_duration(B::Integer, params::OptParams, dur::OptDuration; device::Integer=0)
+    h = Ref{Ptr{Cvoid}}(C_NULL)
+    check(ccall((:qoc_opt_create_duration, libqoc), Cint, (Ptr{Ptr{Cvoid}}, Cint, Cint, Ref{OptParams}, Ref{OptDuration}),
+                h, device, B, params, dur), C_NULL)
+    return h[]
+end
+
+"""
+    minimize_spline_duration!(cache, opt, d_z, max_ticks; poll_every=16) -> ticks
+
+Time-optimal control on the device from start to finish (`qoc_minimize_spline_duration_dev`): minimises
+f = J + time_weight τ over z = [c, τ] for every seed of the cache's context.  `d_z` is a device pointer to
+B x (ns * nu + 1) doubles, the starts in and the final iterates out; the spline basis and a time scale
+(`set_time_scale!`) must be set, and the time scale holds the final τ on return.  Not run, see `set_time_scale!`.
+"""
+function minimize_spline_duration!(c::MI355XCache, opt::Ptr{Cvoid}, d_z::Ptr{Cdouble}, max_ticks::Integer;
+                                   poll_every::Integer=16)
+    ticks = Ref{Clonglong}(0)
+    check(ccall((:qoc_minimize_spline_duration_dev, libqoc), Cint,
+                (Ptr{Cvoid}, Ptr{Cvoid}, Ptr{Cdouble}, Clonglong, Cint, Ptr{Clonglong}),
+                c.ctx, opt, d_z, max_ticks, poll_every, ticks), c.ctx)
+    return Int(ticks[])
+end
+
 """States of the last propagate, fetched lazily (the reference returns cache.x, Nt+1 matrices)."""
 struct LazyStates <: AbstractVector{Matrix{ComplexF64}}
     c::MI355XCache

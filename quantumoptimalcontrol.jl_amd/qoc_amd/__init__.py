@@ -27,7 +27,9 @@ from .engine import GrapeEngine, comm_unique_id, expm, expm_jacobian  # noqa: F4
 from .optimize import (  # noqa: F401
     DeviceOptimizer,
     SplineGrape,
+    SplineGrapeDuration,
     minimize_batched,
+    minimize_duration_on_device,
     minimize_on_device,
     minimize_ticks,
 )
@@ -37,5 +39,5 @@ __all__ = [
     "grape_sensitivity", "propagate", "setup_bilinear_matrices", "setup_grape_cache",
     "setup_infidelity", "setup_infidelity_zcalibrated", "setup_state_penalty", "systems",
     "SplineGrape", "minimize_batched", "propagate_pwc", "compute_pwc_gradient",
-    "DeviceOptimizer", "minimize_on_device", "minimize_ticks",
+    "DeviceOptimizer", "minimize_on_device", "minimize_ticks", "SplineGrapeDuration", "minimize_duration_on_device",
 ]

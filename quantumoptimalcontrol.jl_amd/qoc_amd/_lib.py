@@ -42,6 +42,11 @@ class OptParams(C.Structure):
                 ("max_ls", C.c_int), ("rho0", C.c_double), ("gtol", C.c_double), ("order", C.c_int)]
 
 
+class OptDuration(C.Structure):
+    """qoc_opt_duration (include/qoc.h)."""
+    _fields_ = [("tau_lower", C.c_double), ("tau_upper", C.c_double), ("time_weight", C.c_double)]
+
+
 # Every symbol include/qoc.h declares, with (restype, argtypes).
 _dp = C.POINTER(C.c_double)
 _ip = C.POINTER(C.c_int)
@@ -107,6 +112,7 @@ SIGNATURES = {
     "qoc_sensitivity_spline": (C.c_int, [_vp, _dp, C.c_int, _dp]),
     "qoc_spline_constraints_dev": (C.c_int, [_vp, C.c_void_p, C.c_void_p, C.c_void_p]),
     "qoc_opt_create": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.POINTER(OptParams)]),
+    "qoc_opt_create_duration": (C.c_int, [C.POINTER(_vp), C.c_int, C.c_int, C.POINTER(OptParams), C.POINTER(OptDuration)]),
     "qoc_opt_destroy": (None, [_vp]),
     "qoc_opt_start_dev": (C.c_int, [_vp, _vp, _vp]),
     "qoc_opt_trial_dev": (_vp, [_vp]),
@@ -114,6 +120,7 @@ SIGNATURES = {
     "qoc_opt_field_dev": (_vp, [_vp, C.c_int]),
     "qoc_opt_result": (C.c_int, [_vp, _vp, _dp, _dp, _dp, _dp, _dp, _ip, _ip, _ip, _ip, _ip, _ip, _ip]),
     "qoc_minimize_spline_dev": (C.c_int, [_vp, _vp, _vp, C.c_longlong, C.c_int, C.POINTER(C.c_longlong)]),
+    "qoc_minimize_spline_duration_dev": (C.c_int, [_vp, _vp, _vp, C.c_longlong, C.c_int, C.POINTER(C.c_longlong)]),
     "qoc_gemm_stats": (C.c_int, [_vp, _dp, C.POINTER(C.c_longlong), _dp, C.c_int]),
     "qoc_expm_batched": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, _dp, _dp, _ip, _ip]),
     "qoc_expm_jacobian": (C.c_int, [C.c_int, C.c_int, C.c_int, _dp, C.POINTER(_dp), _dp, C.c_int, C.c_double, _dp]),

@@ -450,6 +450,18 @@ class GrapeEngine:
                                                     C.byref(ticks)))
         return int(ticks.value)
 
+    def minimize_spline_duration_device(self, opt, d_z: int, max_ticks: int, poll_every: int = 16) -> int:
+        """minimize_spline_device with the gate duration as every seed's last variable
+        (qoc_minimize_spline_duration_dev): opt is an optimize.DeviceOptimizer made with ``tau_bounds`` and
+        n = ns * nu + 1; d_z (B x (ns * nu + 1) doubles on the device, rows [c, τ]) holds the starts and receives the
+        final iterates.  A time scale must be set (``set_time_scale``); the call overwrites it and leaves the final τ
+        there.  The result's f is J + time_weight * τ; allgather_best() is the closing eval's (min J, its seed).
+        Returns the ticks the slowest seed used."""
+        ticks = C.c_longlong()
+        self._chk(self._lib.qoc_minimize_spline_duration_dev(self._h, opt._h, C.c_void_p(d_z), int(max_ticks),
+                                                             int(poll_every), C.byref(ticks)))
+        return int(ticks.value)
+
     def stream(self) -> int:
         return self._lib.qoc_stream(self._h)
 

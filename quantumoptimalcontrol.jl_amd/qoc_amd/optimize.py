@@ -130,6 +130,32 @@ class SplineGrapeDuration:
                             (dtau + self.kappa)[:, None]], 1)
         return torch.from_numpy(np.asarray(J) + self.kappa * tau), torch.from_numpy(g)
 
+    def cons(self, z):
+        """The two spline norms of the c part and their (B, 2, n) Jacobian, whose τ column is zero: with ``fg`` the host
+        reference of the constrained run, ``minimize_ticks(obj.fg, z0, lower=lo, upper=hi, cons=obj.cons, g_upper=...)``.
+        A device z runs the engine's constraint kernel on the c part; a host z the torch form."""
+        import torch
+        if isinstance(z, torch.Tensor) and z.is_cuda:
+            B, nc = self.B, self.nc
+            c = z[:, :nc].contiguous()
+            g = torch.empty(B, 2, dtype=torch.float64, device=z.device)
+            gj = torch.empty(B, 2, nc, dtype=torch.float64, device=z.device)
+            torch.cuda.current_stream(z.device).synchronize()
+            self.eng.spline_constraints_device(c.data_ptr(), g.data_ptr(), gj.data_ptr())
+            self.eng.synchronize()
+            return g, torch.cat([gj, torch.zeros(B, 2, 1, dtype=torch.float64, device=z.device)], 2)
+        zh = z if isinstance(z, torch.Tensor) else torch.from_numpy(np.asarray(z, dtype=np.float64))
+        return duration_constraints_torch(zh.reshape(self.B, self.n), self.ns, self.nu)
+
+
+def duration_constraints_torch(z, ns: int, nu: int):
+    """``spline_constraints_torch`` on the c part of z = [c, τ] (B, ns * nu + 1); the Jacobian (B, 2, ns * nu + 1) has a
+    zero τ column."""
+    import torch
+    nc = ns * nu
+    g, gj = spline_constraints_torch(z[:, :nc], ns, nu)
+    return g, torch.cat([gj, torch.zeros(z.shape[0], 2, 1, dtype=gj.dtype, device=gj.device)], 2)
+
 
 def spline_constraints_torch(c, ns: int, nu: int):
     """Reference (torch) form of g = [norm(c), norm(diff(c, dims=1))] and its Jacobian (B, 2, nc)."""
@@ -517,11 +543,15 @@ class DeviceOptimizer:
 
     Everything is queued on ``stream`` (default: torch's current stream on ``device``, so torch objectives need no
     synchronisation; pass ``engine.stream()`` to drive it with engine evals) and nothing waits for the host.
-    ns, nu > 0 adds the spline-norm constraints g = [norm(c), norm(diff(c, dims=1))] <= g_upper, n = ns * nu."""
+    ns, nu > 0 adds the spline-norm constraints g = [norm(c), norm(diff(c, dims=1))] <= g_upper, n = ns * nu.
+    ``tau_bounds=(lo, hi)`` makes the duration form (qoc_opt_create_duration): the last variable is a gate duration with
+    these bounds instead of lower / upper, left out of the constraints, and n = ns * nu + 1; ``time_weight`` is the κ of
+    f = J + κ τ in ``GrapeEngine.minimize_spline_duration_device`` (ask / tell takes the caller's complete f and grad)."""
 
     def __init__(self, B: int, n: int, lower=None, upper=None, ns: int = 0, nu: int = 0, g_upper=None,
                  max_iter: int = 100, memory: int = 10, outer_iters: int = 4, rho0: float = 10.0, gtol: float = 1e-9,
-                 max_ls: int = 12, order: int = 3, device: int = 0, stream: int | None = None):
+                 max_ls: int = 12, order: int = 3, device: int = 0, stream: int | None = None, tau_bounds=None,
+                 time_weight: float = 0.0):
         import ctypes as C
         from . import _lib as L
         from .engine import _order
@@ -534,7 +564,11 @@ class DeviceOptimizer:
                         max_iter=int(max_iter), memory=int(memory), outer_iters=int(outer_iters), max_ls=int(max_ls),
                         rho0=float(rho0), gtol=float(gtol), order=_order(order))
         h = C.c_void_p()
-        L.check(self._lib.qoc_opt_create(C.byref(h), int(device), int(B), C.byref(p)))
+        if tau_bounds is None:
+            L.check(self._lib.qoc_opt_create(C.byref(h), int(device), int(B), C.byref(p)))
+        else:
+            d = L.OptDuration(tau_lower=float(tau_bounds[0]), tau_upper=float(tau_bounds[1]), time_weight=float(time_weight))
+            L.check(self._lib.qoc_opt_create_duration(C.byref(h), int(device), int(B), C.byref(p), C.byref(d)))
         self._h = h
         self.B, self.n, self.device, self.constrained = int(B), int(n), int(device), bool(ns)
         self._stream = stream
@@ -638,6 +672,37 @@ def minimize_on_device(engine, Bs, c0, lower=None, upper=None, g_upper=None, max
     try:
         ticks = engine.minimize_spline_device(opt, c.data_ptr(), opt.max_ticks if max_ticks is None else max_ticks,
                                               poll_every)
+        return opt.result(ticks)
+    finally:
+        opt.close()
+
+
+def minimize_duration_on_device(engine, Bs, z0, lower, upper, tau_bounds, time_weight: float,
+                                g_upper=None, max_iter: int = 100, memory: int = 10, outer_iters: int = 4,
+                                rho0: float = 10.0, gtol: float = 1e-9, max_ls: int = 12, order: int = 3,
+                                max_ticks: int | None = None, poll_every: int = 16) -> TickResult:
+    """Time-optimal control on the GPU from start to finish: ``minimize_on_device`` over z = [c, τ] (B, ns * nu + 1) with
+    f = J(c; τ) + time_weight * τ (``GrapeEngine.minimize_spline_duration_device``), seed by seed the run of
+    ``minimize_ticks(SplineGrapeDuration(engine, Bs, order, time_weight).fg, z0, ...)`` with per-variable bounds.
+    lower / upper bound c, ``tau_bounds`` τ; g_upper bounds the two spline norms of c (None: unbounded, one round).  A time
+    scale of ones is set first when none is set; on return the engine's time scale holds the final τ, ``result.c`` the
+    final z, ``result.f`` is J + time_weight * τ and ``engine.allgather_best()`` is (min J, its seed) of the closing eval."""
+    import torch
+    engine.set_spline_basis(Bs)
+    ns, nu, B = engine.ns, engine.nu, engine.B
+    if not engine.time_scale_device():
+        engine.set_time_scale(np.ones(B))
+    dev = torch.device("cuda", engine.device)
+    z = torch.as_tensor(z0).to(device=dev, dtype=torch.float64).reshape(B, ns * nu + 1).clone().contiguous()
+    torch.cuda.current_stream(dev).synchronize()  # z is produced on torch's stream
+    if g_upper is None:
+        g_upper, outer_iters = (np.inf, np.inf), 1
+    opt = DeviceOptimizer(B, ns * nu + 1, lower, upper, ns=ns, nu=nu, g_upper=g_upper, max_iter=max_iter, memory=memory,
+                          outer_iters=outer_iters, rho0=rho0, gtol=gtol, max_ls=max_ls, order=order,
+                          device=engine.device, stream=engine.stream(), tau_bounds=tau_bounds, time_weight=time_weight)
+    try:
+        ticks = engine.minimize_spline_duration_device(opt, z.data_ptr(), opt.max_ticks if max_ticks is None else max_ticks,
+                                                       poll_every)
         return opt.result(ticks)
     finally:
         opt.close()

@@ -6,11 +6,19 @@
   sweep   what a gate-time sweep gains: 16 durations x 16 seeds in one context (B = 256, set_time_scale) against the
           caller's form without it, 16 contexts of B = 16 with τ-scaled generators evaluated back to back (each waits
           for the one before it through an event: one stream's order), cavity and zz, order 3
+  optimise  time-optimal control end to end on zz (N = 9, Nt = 500, B = 512, 10 splines, order 3 and exact), z = [c, τ],
+          f = J + 0.05 τ, |c| <= 0.4, 0.5 <= τ <= 2, the same starts and the same number of ticks (--ticks, 600; gtol = 0, so no seed stops early) in:
+          (a) the host-driven drivers over SplineGrapeDuration.fg with a device z: minimize_ticks stopped after that many
+              ticks, and minimize_batched with as many iterations as give about that many batched evals
+          (b) minimize_on_device at fixed τ (the starts' own), stopped after that many ticks
+          (c) minimize_duration_on_device stopped after that many ticks
+          one warm-up of every leg, then 3 rounds in which the legs take turns; ticks/s of every repeat, and for (a) and
+          (c) the accepted iterations per seed and the best f
 Warm-up of 20 steps, then K = 200 timed steps between two synchronisations, 3 repeats, every repeat printed, one
 process at a time.
 --parent DIR times the package of another checkout (built there) with this tool: a library from before the time scale
 has the plain and the contexts legs only.
-Usage: python tools/bench_duration.py [flag|sweep ...] [--steps K] [--parent DIR]"""
+Usage: python tools/bench_duration.py [flag|sweep|optimise ...] [--steps K] [--ticks T] [--parent DIR]"""
 import os
 import sys
 import time
@@ -30,6 +38,11 @@ K = 200
 if "--steps" in args:
     _i = args.index("--steps")
     K = max(1, int(args[_i + 1]))
+    del args[_i:_i + 2]
+TICKS = 600
+if "--ticks" in args:
+    _i = args.index("--ticks")
+    TICKS = max(1, int(args[_i + 1]))
     del args[_i:_i + 2]
 WARM, REPEATS = 20, 3
 parts = args or ["flag", "sweep"]
@@ -156,6 +169,72 @@ def part_sweep():
             x.close()
 
 
+def part_optimise():
+    from qoc_amd import optimize as opt
+    has_dur = hasattr(opt, "minimize_duration_on_device")
+    prob, _, B, _ = problem("zz")
+    ns, nu, kappa = 10, prob.nu, 0.05
+    nc = ns * nu
+    Bs = systems.spline_matrix(20.0, prob.Nt, ns)  # zz_batch's gate time
+    rng = np.random.default_rng(4)
+    z0 = np.concatenate([rng.uniform(-0.3, 0.3, size=(B, nc)), rng.uniform(0.8, 1.6, size=(B, 1))], 1)
+    z0d = torch.from_numpy(z0).cuda()
+    c0d = z0d[:, :nc].contiguous()
+    lo = np.concatenate([np.full(nc, -0.4), [0.5]])
+    hi = np.concatenate([np.full(nc, 0.4), [2.0]])
+    big = 10 ** 6  # iterations per round: no seed ends before the ticks run out
+    for order in (3, "exact"):
+        e = make(prob, B)
+        e.set_time_scale(z0[:, nc])
+        obj = opt.SplineGrapeDuration(e, Bs, order=order, time_weight=kappa)
+
+        def host_ticks():
+            r = opt.minimize_ticks(obj.fg, z0d, lower=lo, upper=hi, max_iter=big, gtol=0.0, max_ticks=TICKS)
+            return r.ticks, r.iters.cpu().numpy(), float(r.f.min())
+
+        def host_lockstep():  # a line search takes 1-2 batched evals here: TICKS / 2 iterations, the evals counted
+            r = opt.minimize_batched(obj.fg, z0d, lower=lo, upper=hi, max_iter=max(1, TICKS // 2), gtol=0.0)
+            return r.n_evals, np.full(B, len(r.history)), float(r.f.min())
+
+        def fixed_tau():
+            e.set_time_scale(z0[:, nc])
+            r = opt.minimize_on_device(e, Bs, c0d, lower=-0.4, upper=0.4, max_iter=big, gtol=0.0, order=order, max_ticks=TICKS)
+            return r.ticks, r.iters.cpu().numpy(), float(r.f.min())
+
+        def duration():
+            r = opt.minimize_duration_on_device(e, Bs, z0d, -0.4, 0.4, (0.5, 2.0), kappa, max_iter=big, gtol=0.0, order=order,
+                                                max_ticks=TICKS)
+            return r.ticks, r.iters.cpu().numpy(), float(r.f.min())
+
+        legs = {"(a) host ticks": host_ticks, "(a) host lockstep": host_lockstep, "(b) device fixed tau": fixed_tau}
+        if has_dur:
+            legs["(c) device duration"] = duration
+        rates, last = {k: [] for k in legs}, {}
+        for rnd in range(-1, REPEATS):  # -1: warm-up
+            for k, fn in legs.items():
+                e.synchronize()
+                torch.cuda.synchronize()
+                t = time.perf_counter()
+                last[k] = fn()
+                e.synchronize()
+                torch.cuda.synchronize()
+                if rnd >= 0:
+                    rates[k].append(last[k][0] / (time.perf_counter() - t))
+        tag = f"optimise zz B={B} ns={ns} order {order} ticks {TICKS}"
+        for k, r in rates.items():
+            n, it, best = last[k]
+            print(f"{tag} {k:21s} " + " ".join(f"{x:9.1f}" for x in r) + f" ticks/s  (batched evals {n})"
+                  + ("" if k.startswith("(b)") else f"  accepted iterations per seed min {it.min()} median "
+                     f"{np.median(it):.0f} max {it.max()}  best f {best:.9e}"), flush=True)
+        med = {k: np.median(r) for k, r in rates.items()}
+        print(f"{tag}: (b) / (a) host ticks = {med['(b) device fixed tau'] / med['(a) host ticks']:.1f}, (b) / (a) host "
+              f"lockstep = {med['(b) device fixed tau'] / med['(a) host lockstep']:.1f}"
+              + (f"; (c) / (a) host ticks = {med['(c) device duration'] / med['(a) host ticks']:.1f}, (c) / (a) host "
+                 f"lockstep = {med['(c) device duration'] / med['(a) host lockstep']:.1f}, (c) / (b) = "
+                 f"{med['(c) device duration'] / med['(b) device fixed tau']:.3f}" if has_dur else ""), flush=True)
+        e.close()
+
+
 torch.cuda.set_device(0)
 for p in parts:
-    {"flag": part_flag, "sweep": part_sweep}[p]()
+    {"flag": part_flag, "sweep": part_sweep, "optimise": part_optimise}[p]()
